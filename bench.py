@@ -9,12 +9,19 @@ Inputs are resident in HBM before the timed region.  One process per GPU; clips 
 run N clips with no collective in the loop (weak scaling): RCCL is used once for the packed-weight broadcast
 and once for the metric all-gather.
 
-    python bench.py [--gpus N --steps K --warmup W]                      # N=1
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]   # N=1
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (see the contract in the task statement) including
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 (metric, value, unit,
+higher_is_better, dtype, ms_per_step = wall milliseconds of one timed step, ...).
+--dump-outputs DIR writes rank 0's latents after the last timed step as DIR/latents.npy (float32); the weights
+and inputs are seeded, so two builds run with the same arguments can be compared output for output.
+--full adds the legs beyond the headline figure (each can still be switched off with its --no-* option):
+  vae_decode    the SD1.5 VAE decoder on the denoised clip
   roofline      dominant kernel family = the bf16 MFMA GEMM/conv kernels: algorithmic FLOPs of all their
                 launches in one step / their summed HIP-event durations (instrumented eager step)
+  batched       --also-clips clips per forward and the {2, 4, 8} clips sweep (N=1 only)
+  precise       the in-tolerance precision modes with their rel-L2 against the reference output (N=1 only)
   cpu_baseline  the oracle (oracle/unet_ref.py, fp32, torch CPU) timed on this box's host cores on the same
                 CFG forward (rank 0, N=1 only)
 """
@@ -214,12 +221,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
     ap.add_argument("--save-tiles", default="", help="write the autotuned tile table here (reload with AVSD_TILE_CACHE=<file>)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the latents of the last step (rank 0) as DIR/latents.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: VAE decode, roofline, batched clips, precision modes, "
+                         "CPU baseline (the --no-* options below switch single legs off again)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-vae", action="store_true", help="skip the VAE-decode leg")
     ap.add_argument("--no-precise", action="store_true", help="skip the split-precision leg")
     ap.add_argument("--also-clips", type=int, default=4,
-                    help="after the headline measurement, also time this many clips batched into one forward per GPU "
+                    help="with --full, after the headline measurement, also time this many clips batched into one forward per GPU "
                          "(BASELINE cfg 3 runs 4 per GPU); 0 = skip")
     ap.add_argument("--fp8-attention", action="store_true",
                     help="BASELINE cfg 5: e4m3 Q/K/V in the first-frame and cross attentions (f32 softmax / accumulation)")
@@ -228,6 +240,12 @@ def main():
                     help="independent clips batched into one UNet forward per GPU (BASELINE cfg 3 uses 4); "
                          "the default 1 is BASELINE cfg 2 / the reference's one-clip-per-call")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:
+        # a plain run measures the headline figure only
+        a.no_vae = a.no_roofline = a.no_precise = a.no_cpu_baseline = True
+        a.also_clips = 0
 
     from asva_amd import dist as adist
     from asva_amd import ops
@@ -292,6 +310,12 @@ def main():
     wall = time.perf_counter() - t0
     gpu_ms = ev0.elapsed_time(ev1)
     finite = bool(torch.isfinite(latents).all())
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path receives: the latents, updated in place by the last step ((clips, 4, 12, 32, 32), 0.2 MB a clip)
+        import numpy as np
+
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "latents.npy"), latents.detach().float().cpu().numpy())
 
     vae_wall, vae_reps = 0.0, 5
     if not a.no_vae:

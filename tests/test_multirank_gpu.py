@@ -26,7 +26,7 @@ def _env(**extra):
 
 
 def test_bench_two_ranks_on_one_gpu():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline",
                         "--no-roofline", "--no-precise", "--also-clips", "0"],
                        env=_env(AVSD_DIST_SAME_DEVICE="1", AVSD_DIST_BACKEND="gloo"), capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])

@@ -20,7 +20,8 @@ print('$1 step %.2f steps/s (%.3f ms)   4 clips %s clip-steps/s   VAE %s clips/s
 for i in $(seq $REPS); do
   for t in new old; do
     if [ $t = old ]; then D=$OLD; else D=$GRAFT_REPO_ROOT; fi
-    (cd $D && python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-roofline --no-precise --also-clips 4 2>/dev/null | row "$t($( [ $t = old ] && echo $TAG || echo HEAD))")
+    F=$(grep -q -- '"--full"' $D/bench.py && echo --full)    # trees older than --full run every leg by default
+    (cd $D && python bench.py --steps 40 --warmup 5 $F --no-cpu-baseline --no-roofline --no-precise --also-clips 4 2>/dev/null | row "$t($( [ $t = old ] && echo $TAG || echo HEAD))")
   done
 done
 for t in new old; do
