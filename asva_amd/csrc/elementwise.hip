@@ -141,6 +141,40 @@ __global__ void guided_step_kernel(const GuidedArgs a) {
   }
 }
 
+struct MultistepArgs {
+  const float* noise_pred; float* hist; const float* x_in; float* x_out;
+  int n_branch, store_slot, n_hist;
+  int hist_idx[4];
+  float w[4];
+  float g, g2, ca, c_cur, s_x, s_e;
+  int B, C, F, HW;
+};
+
+// DPM-Solver++ step: the ring holds data predictions d = s_x x + s_e eps of earlier steps (include/avsd.h)
+__global__ void guided_multistep_kernel(const MultistepArgs a) {
+  const int64_t per = (int64_t)a.B * a.C * a.F * a.HW;
+  const int64_t fhw = (int64_t)a.F * a.HW;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < per; i += (int64_t)gridDim.x * blockDim.x) {
+    float eps = a.noise_pred[i];
+    if (a.n_branch >= 2) {      // the guidance rule of guided_step_kernel
+      const float e1 = a.noise_pred[per + i];
+      float gsum = eps + a.g * (e1 - eps);
+      if (a.n_branch == 3) gsum = gsum + a.g2 * (a.noise_pred[2 * per + i] - e1);
+      eps = gsum;
+    }
+    const float xin = a.x_in[i];
+    const float d = fmaf(a.s_x, xin, a.s_e * eps);
+    if (a.hist && a.store_slot >= 0) a.hist[(int64_t)a.store_slot * per + i] = d;
+    float acc = fmaf(a.c_cur, d, a.ca * xin);
+    for (int k = 0; k < a.n_hist; ++k) {
+      const float h = (a.hist_idx[k] == a.store_slot) ? d : a.hist[(int64_t)a.hist_idx[k] * per + i];
+      acc = fmaf(a.w[k], h, acc);
+    }
+    const int f = (int)((i % fhw) / a.HW);
+    a.x_out[i] = (f == 0) ? xin : acc;
+  }
+}
+
 __global__ void vae_postprocess_kernel(const h16_t* src, int ld, int64_t src_lo, float* dst, int N, int HW) {
   const int64_t n = (int64_t)N * 3 * HW;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -291,6 +325,27 @@ extern "C" int avsd_guided_step(const float* noise_pred, int n_branch, float g, 
   const int64_t n = (int64_t)B * C * F * HW;
   hipLaunchKernelGGL(guided_step_kernel, dim3(grid_for(n, 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
   AVSD_CHECK_LAUNCH("guided_step launch");
+  return AVSD_OK;
+}
+
+extern "C" int avsd_guided_multistep(const float* noise_pred, int n_branch, float g, float g2, float* hist, int store_slot,
+                                     const int32_t* hist_idx, const float* w, int n_hist, const float* x_in, float* x_out,
+                                     float ca, float c_cur, float s_x, float s_e, int B, int C, int F, int HW, void* stream) {
+  AVSD_REQUIRE(noise_pred && x_in && x_out, "guided_multistep: null pointer");
+  AVSD_REQUIRE(n_branch >= 1 && n_branch <= 3, "guided_multistep: n_branch must be 1, 2 or 3");
+  AVSD_REQUIRE(n_hist >= 0 && n_hist <= 4, "guided_multistep: n_hist must be in [0, 4]");
+  AVSD_REQUIRE((n_hist == 0 && store_slot < 0) || hist, "guided_multistep: history requested without hist");
+  AVSD_REQUIRE(n_hist == 0 || (hist_idx && w), "guided_multistep: null history tables");
+  AVSD_REQUIRE(B > 0 && C > 0 && F > 0 && HW > 0, "guided_multistep: bad shape");
+  MultistepArgs a;
+  a.noise_pred = noise_pred; a.hist = hist; a.x_in = x_in; a.x_out = x_out;
+  a.n_branch = n_branch; a.store_slot = store_slot; a.n_hist = n_hist;
+  for (int k = 0; k < 4; ++k) { a.hist_idx[k] = k < n_hist ? hist_idx[k] : 0; a.w[k] = k < n_hist ? w[k] : 0.f; }
+  a.g = g; a.g2 = g2; a.ca = ca; a.c_cur = c_cur; a.s_x = s_x; a.s_e = s_e;
+  a.B = B; a.C = C; a.F = F; a.HW = HW;
+  const int64_t n = (int64_t)B * C * F * HW;
+  hipLaunchKernelGGL(guided_multistep_kernel, dim3(grid_for(n, 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  AVSD_CHECK_LAUNCH("guided_multistep launch");
   return AVSD_OK;
 }
 

@@ -1201,6 +1201,30 @@ def guided_step(noise_pred: torch.Tensor, n_branch: int, g: float, x_in: torch.T
           "avsd_guided_step")
 
 
+def guided_multistep(noise_pred: torch.Tensor, n_branch: int, g: float, x_in: torch.Tensor, x_out: torch.Tensor,
+                     ca: float, c_cur: float, s_x: float, s_e: float, *, hist: Optional[torch.Tensor] = None, store_slot: int = -1,
+                     hist_idx=(), w=(), g2: float = 0.0) -> None:
+    """avsd_guided_multistep (include/avsd.h): one DPM-Solver++ step in place or out of place; `hist` is (slots, *x_in.shape)."""
+    _req(noise_pred, F32, "noise_pred")
+    _req(x_in, F32, "x_in")
+    _req(x_out, F32, "x_out")
+    B, Cc, Fr, H, W = x_in.shape
+    if not (x_in.is_contiguous() and x_out.is_contiguous() and x_out.shape == x_in.shape and noise_pred.is_contiguous()
+            and noise_pred.numel() == n_branch * x_in.numel()):
+        raise ValueError("guided_multistep: contiguous x_in / x_out of one shape and noise_pred of n_branch times their size")
+    slots = [s for s in (store_slot, *hist_idx) if s >= 0]
+    if slots and (hist is None or not hist.is_contiguous() or hist.dtype != F32 or tuple(hist.shape[1:]) != tuple(x_in.shape)
+                  or max(slots) >= hist.shape[0] or min(hist_idx, default=0) < 0):
+        raise ValueError(f"guided_multistep: slots {slots} need a contiguous f32 hist of shape (> {max(slots)}, {tuple(x_in.shape)})")
+    nh = len(hist_idx)
+    idx = (C.c_int32 * 4)(*(list(hist_idx) + [0] * (4 - nh)))
+    ws = (C.c_float * 4)(*(list(w) + [0.0] * (4 - nh)))
+    check(_lib.lib().avsd_guided_multistep(_p(noise_pred), n_branch, float(g), float(g2), _p(hist), store_slot, idx, ws, nh,
+                                           _p(x_in), _p(x_out), float(ca), float(c_cur), float(s_x), float(s_e), B, Cc, Fr, H * W,
+                                           _stream()),
+          "avsd_guided_multistep")
+
+
 def vae_postprocess(rows: torch.Tensor, n_img: int, H: int, W: int) -> torch.Tensor:
     _req(rows, P.ACT, "rows")
     out = torch.empty((n_img, 3, H, W), dtype=F32, device=rows.device)

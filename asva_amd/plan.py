@@ -229,6 +229,18 @@ def export_steps(path: str, timesteps, plans) -> None:
                                 int(p.save_sample), int(p.use_saved_sample), *[int(i) for i in idx], *[float(x) for x in w]))
 
 
+def export_multistep_steps(path: str, timesteps, plans) -> None:
+    """The scalar schedule of a DPM-Solver++ run (schedulers.MultistepPlan: coefficients of avsd_guided_multistep) as the binary
+    table tools/plan_host.cpp's `denoise_ms` reads: per step  f32 t, ca, c_cur, s_x, s_e; i32 store_slot, n_hist; i32 hist_idx[4];
+    f32 hist_w[4]."""
+    with open(path, "wb") as f:
+        for t, p in zip(timesteps, plans):
+            idx = list(p.hist_idx) + [0] * (4 - len(p.hist_idx))
+            w = list(p.hist_w) + [0.0] * (4 - len(p.hist_w))
+            f.write(struct.pack("<5f2i4i4f", float(t), float(p.ca), float(p.c_cur), float(p.s_x), float(p.s_e), int(p.store_slot),
+                                len(p.hist_idx), *[int(i) for i in idx], *[float(x) for x in w]))
+
+
 class Bundle:
     """A saved bundle, replayed in-process through the C API (what tools/plan_host.cpp does from C++)."""
 

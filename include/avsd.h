@@ -353,6 +353,20 @@ int avsd_guided_step(const float* noise_pred, int n_branch, float g, float g2, f
                      const float* w_host, int n_hist, const float* x_in, float* x_out, float ca,
                      float cb, int B, int C, int F, int HW, void* stream);
 
+/* Guidance + DPM-Solver++ multistep update on (B, C, F, H, W) f32 latents, frame 0 pinned:
+ *   eps      = guidance combine of noise_pred (n_branch 1 / 2 / 3, g, g2: exactly the rule of avsd_guided_step)
+ *   d        = s_x * x_in + s_e * eps        (data prediction x0 = (x - sigma_t eps) / alpha_t: s_x = 1 / alpha_t,
+ *                                             s_e = -sigma_t / alpha_t; s_x = 0, s_e = 1 gives eps itself)
+ *   hist[store_slot] = d                     (if store_slot >= 0; hist holds slots of B*C*F*HW floats)
+ *   x_out[:, :, 1:] = ca * x_in + c_cur * d + sum_k w[k] * hist[hist_idx[k]]   (n_hist <= 4 terms; the slot stored by
+ *                                             this call is read from the value just computed) ;  x_out[:, :, 0] = x_in[:, :, 0]
+ * x_in == x_out (in place) is allowed.  DPM-Solver++ 1M / 2M / 3M (asva_amd/schedulers.py DPMSolverMultistepScheduler,
+ * coefficients on the host) is of this form; PNDM and DDIM stay on avsd_guided_step. */
+int avsd_guided_multistep(const float* noise_pred, int n_branch, float g, float g2, float* hist, int store_slot,
+                          const int32_t* hist_idx_host, const float* w_host, int n_hist, const float* x_in,
+                          float* x_out, float ca, float c_cur, float s_x, float s_e, int B, int C, int F,
+                          int HW, void* stream);
+
 /* VAE post-processing (pipeline_audio_cond_animation.py:212): channels-last bf16
  * [N*H*W][ld] (3 channels) -> (N, 3, H, W) f32 = clamp(x / 2 + 0.5, 0, 1). */
 int avsd_vae_postprocess(const void* src, int ld, float* dst, int N, int HW, void* stream);

@@ -1,8 +1,9 @@
 """Writes a launch-plan bundle (include/avsd.h "launch plans", asva_amd/plan.py) for the AVSync15 geometry of BASELINE.json
 configs[1]: SD1.5 UNet3D (random-init, seeded), one 12 x 256 x 256 clip, audio-only guidance (CFG batch 2), 50-step PLMS
-table, SD1.5 VAE decode — and the program file that makes tools/plan_host.cpp run the whole clip without Python.
+table (--scheduler ddim / dpmsolver++: DDIM or DPM-Solver++; the latter writes steps_ms.bin for plan_host's `denoise_ms`), SD1.5
+VAE decode — and the program file that makes tools/plan_host.cpp run the whole clip without Python.
 
-    python tools/export_plan.py --out /tmp/avsync15 [--steps 50] [--no-vae]
+    python tools/export_plan.py --out /tmp/avsync15 [--steps 50] [--no-vae] [--scheduler {pndm,ddim,dpmsolver++}] [--solver-order 2]
     asva_amd/plan_host asva_amd/libavsd_hip.so /tmp/avsync15/clip.plan /tmp/avsync15/program.txt
 
 Also runs the same clip through the Python DenoiseEngine and stores its final latents / frames (expected.*.bin) so the two
@@ -26,6 +27,8 @@ def main():
     ap.add_argument("--out", default="/tmp/avsync15")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--no-vae", action="store_true")
+    ap.add_argument("--scheduler", choices=("pndm", "ddim", "dpmsolver++"), default="pndm")
+    ap.add_argument("--solver-order", type=int, default=2, help="DPM-Solver++ order (1, 2 or 3)")
     ap.add_argument("--check", default=None, help="compare <dir>/latents.out, frames.out (written by plan_host) with expected.*.bin")
     a = ap.parse_args()
     if a.check:
@@ -42,7 +45,7 @@ def main():
     from asva_amd import plan, precision as P, unet as U
     from asva_amd.conditioning import audio_segment_mask
     from asva_amd.engine import DenoiseEngine
-    from asva_amd.schedulers import PNDMScheduler
+    from asva_amd.schedulers import DDIMScheduler, DPMSolverMultistepScheduler, PNDMScheduler
 
     dev = torch.device("cuda", 0)
     os.makedirs(a.out, exist_ok=True)
@@ -84,13 +87,22 @@ def main():
     b = rec.save(os.path.join(a.out, "clip.plan"))
     print("bundle:", b.n_calls, f"launches; {len(b.buffer_sizes())} buffers, {sum(b.buffer_sizes()) / 1e9:.2f} GB")
     b.close()
-    eng = DenoiseEngine(unet, PNDMScheduler(), audio_guidance_scale=4.0)
+    if a.scheduler == "dpmsolver++":
+        sched = DPMSolverMultistepScheduler(solver_order=a.solver_order)
+    else:
+        sched = PNDMScheduler() if a.scheduler == "pndm" else DDIMScheduler()
+    eng = DenoiseEngine(unet, sched, audio_guidance_scale=4.0)
     eng.prepare(lat0, a.steps)
-    plan.export_steps(os.path.join(a.out, "steps.bin"), eng._ts.tolist(), eng._plans)
+    if a.scheduler == "dpmsolver++":
+        steps_file, denoise = "steps_ms.bin", "denoise_ms"
+        plan.export_multistep_steps(os.path.join(a.out, steps_file), eng._ts.tolist(), eng._plans)
+    else:
+        steps_file, denoise = "steps.bin", "denoise"
+        plan.export_steps(os.path.join(a.out, steps_file), eng._ts.tolist(), eng._plans)
     for name, tns in (("text", text), ("audio", audio), ("latents", lat0)):
         _bytes(tns).cpu().numpy().tofile(os.path.join(a.out, name + ".in"))
     prog = [f"load text {a.out}/text.in", f"load audio {a.out}/audio.in", f"load latents {a.out}/latents.in", "run set_conditioning",
-            f"denoise {a.out}/steps.bin latents x t noise_pred 2 4.0 0.0 1 4 12 1024", f"save latents {a.out}/latents.out"]
+            f"{denoise} {a.out}/{steps_file} latents x t noise_pred 2 4.0 0.0 1 4 12 1024", f"save latents {a.out}/latents.out"]
     if vae is not None:
         prog += ["run decode", f"save frames {a.out}/frames.out"]
     open(os.path.join(a.out, "program.txt"), "w").write("\n".join(prog) + "\n")
@@ -101,7 +113,7 @@ def main():
     if vae is not None:
         _bytes(vae.decode_to_uint8_frames(want)).cpu().numpy().tofile(os.path.join(a.out, "expected.frames.bin"))
     torch.cuda.synchronize()
-    print(f"wrote {a.out}: clip.plan, clip.plan.d/, steps.bin ({len(eng._plans)} UNet evaluations), program.txt, expected.*.bin")
+    print(f"wrote {a.out}: clip.plan, clip.plan.d/, {steps_file} ({len(eng._plans)} UNet evaluations), program.txt, expected.*.bin")
 
 
 if __name__ == "__main__":

@@ -13,6 +13,9 @@
 //                                              guidance + scheduler update in place (avsd_guided_step), frame 0 pinned
 //                                              PLAN_HOST_GRAPH=1: the forward plan is captured once into a hipGraph and
 //                                              replayed (avsd_plan_run only issues launches on the stream it is given)
+//   denoise_ms <steps_ms.bin> <latents> <x> <t> <noise> <n_branch> <g> <g2> <B> <C> <F> <HW>
+//                                              the same loop with a DPM-Solver++ table (asva_amd/plan.py:
+//                                              export_multistep_steps): the update is avsd_guided_multistep
 //   copy <src> <dst> <bytes>                   device-to-device between regions
 //   save <region> <file>                       download a region to a file
 // <latents>, <x>, <t>, <noise> and the names after load / save / copy are REGION names of the bundle.
@@ -55,6 +58,7 @@ struct Api {
   decltype(&avsd_plan_num_calls) num_calls;
   decltype(&avsd_plan_run) run;
   decltype(&avsd_guided_step) guided_step;
+  decltype(&avsd_guided_multistep) guided_multistep;
   decltype(&avsd_copy) copy;
 };
 
@@ -71,6 +75,14 @@ static void sym(void* h, const char* name, T& fn) {
 struct Step {
   float t, ca, cb, w_cur;
   int32_t store_slot, n_hist, save_sample, use_saved;
+  int32_t hist_idx[4];
+  float hist_w[4];
+};
+
+// one entry of the DPM-Solver++ table (asva_amd/plan.py: export_multistep_steps; schedulers.MultistepPlan)
+struct MsStep {
+  float t, ca, c_cur, s_x, s_e;
+  int32_t store_slot, n_hist;
   int32_t hist_idx[4];
   float hist_w[4];
 };
@@ -109,6 +121,7 @@ int main(int argc, char** argv) {
   sym(h, "avsd_plan_num_calls", api.num_calls);
   sym(h, "avsd_plan_run", api.run);
   sym(h, "avsd_guided_step", api.guided_step);
+  sym(h, "avsd_guided_multistep", api.guided_multistep);
   sym(h, "avsd_copy", api.copy);
 #define AVSD_OK_OR_DIE(x)                                                              \
   do {                                                                                 \
@@ -205,14 +218,16 @@ int main(int argc, char** argv) {
       long long bytes;
       ss >> s >> d >> bytes;
       AVSD_OK_OR_DIE(api.copy(reg(s).ptr, reg(d).ptr, bytes, 1, stream));
-    } else if (cmd == "denoise") {
+    } else if (cmd == "denoise" || cmd == "denoise_ms") {
+      const bool dpm = cmd == "denoise_ms";
       std::string file, lat, x, t, noise;
       int n_branch, B, Cc, Fr, HW;
       float g, g2;
       ss >> file >> lat >> x >> t >> noise >> n_branch >> g >> g2 >> B >> Cc >> Fr >> HW;
       const std::vector<unsigned char> raw = read_file(file);
-      const size_t n = raw.size() / sizeof(Step);
+      const size_t n = raw.size() / (dpm ? sizeof(MsStep) : sizeof(Step));
       const Step* steps = reinterpret_cast<const Step*>(raw.data());
+      const MsStep* ms_steps = reinterpret_cast<const MsStep*>(raw.data());
       const int64_t lat_bytes = (int64_t)B * Cc * Fr * HW * 4;
       float *hist = nullptr, *saved = nullptr;
       HIP_OK(hipMalloc(&hist, (size_t)(4 * lat_bytes)));
@@ -223,6 +238,10 @@ int main(int argc, char** argv) {
       const float* np_ = reinterpret_cast<const float*>(reg(noise).ptr);
       if (reg(lat).bytes != lat_bytes || reg(x).bytes != lat_bytes) {
         fprintf(stderr, "plan_host: denoise: B x C x F x HW does not match the latent regions\n");
+        return 1;
+      }
+      if (dpm && (n_branch < 1 || reg(noise).bytes < n_branch * lat_bytes)) {
+        fprintf(stderr, "plan_host: denoise_ms: region %s holds fewer than %d noise predictions\n", noise.c_str(), n_branch);
         return 1;
       }
       const int kf = plan("forward");
@@ -243,11 +262,24 @@ int main(int argc, char** argv) {
       HIP_OK(hipEventCreate(&e1));
       HIP_OK(hipEventRecord(e0, stream));
       for (size_t i = 0; i < n; ++i) {
-        const Step& s = steps[i];
         AVSD_OK_OR_DIE(api.copy(latents, xp, lat_bytes, 1, stream));
-        HIP_OK(hipMemcpyAsync(tp, &s.t, 4, hipMemcpyHostToDevice, stream));
+        HIP_OK(hipMemcpyAsync(tp, dpm ? &ms_steps[i].t : &steps[i].t, 4, hipMemcpyHostToDevice, stream));
         if (gexec) HIP_OK(hipGraphLaunch(gexec, stream));
         else AVSD_OK_OR_DIE(api.run(b, kf, stream));
+        if (dpm) {
+          const MsStep& m = ms_steps[i];
+          bool ok = m.store_slot < 4 && m.n_hist >= 0 && m.n_hist <= 4;
+          for (int k = 0; ok && k < m.n_hist; ++k) ok = m.hist_idx[k] >= 0 && m.hist_idx[k] < 4;
+          if (!ok) {
+            fprintf(stderr, "plan_host: %s step %zu names a history slot outside the 4-slot ring\n", file.c_str(), i);
+            return 1;
+          }
+          AVSD_OK_OR_DIE(api.guided_multistep(np_, n_branch, g, g2, hist, m.store_slot, m.n_hist ? m.hist_idx : nullptr,
+                                              m.n_hist ? m.hist_w : nullptr, m.n_hist, latents, latents, m.ca, m.c_cur, m.s_x,
+                                              m.s_e, B, Cc, Fr, HW, stream));
+          continue;
+        }
+        const Step& s = steps[i];
         if (s.save_sample) AVSD_OK_OR_DIE(api.copy(latents, saved, lat_bytes, 1, stream));
         AVSD_OK_OR_DIE(api.guided_step(np_, n_branch, g, g2, hist, s.store_slot, s.w_cur,
                                        s.n_hist ? s.hist_idx : nullptr, s.n_hist ? s.hist_w : nullptr, s.n_hist,
