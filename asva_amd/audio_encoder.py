@@ -223,7 +223,7 @@ class ImageBindSegmaskAudioEncoder(nn.Module):
     # -- kernel-side weights ------------------------------------------------------------------------------------
     def pack(self):
         """bf16 GEMM operands, f32 biases / norm parameters / tables, on the module's device."""
-        key = (P.ACT, P.SPLIT, str(self.device))
+        key = (P.pack_key(), str(self.device))
         if self._packed is not None and self._packed.get("key") == key:
             return self._packed
         from .weights import to_act

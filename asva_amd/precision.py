@@ -95,6 +95,18 @@ def plan_key():
     return None if PLAN is None else tuple(sorted(PLAN["three_pass"]))
 
 
+# The upsamplers' nearest-2x upsample + 3x3 convolution (the UNet's FFSpatioTempResUpsample3D, the VAE decoder's Upsample2D) packed as
+# four 2x2 convolutions on the original image, one per output-pixel parity (weights.subpixel_conv3x3): the same function with 4/9 of
+# the multiplies — 0.41 of the UNet step's 5.4 TFLOP become 0.18, 2.09 of the decoder's 7.47 TFLOP per 12 x 256 x 256 clip become 0.93.
+# Assign False for the 3x3 form on the upsampled image; models are repacked on next use.
+SUBPIXEL_UPS = os.environ.get("AVSD_SUBPIXEL_UPS", "1") != "0"
+
+
+def pack_key():
+    """everything process-wide that a packed copy of a model's weights depends on: pack() keeps its copy while this stays the same"""
+    return (ACT, SPLIT, plan_key(), SUBPIXEL_UPS)
+
+
 if os.environ.get("AVSD_PRECISION"):
     set_precision(os.environ["AVSD_PRECISION"])
 if os.environ.get("AVSD_SPLIT", "0") != "0":

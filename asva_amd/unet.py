@@ -24,7 +24,7 @@ from . import precision as P
 
 from . import ops
 from .conditioning import mask_to_key_index
-from .weights import from_act, is_twin, pack_conv1x1, pack_conv3x3, pack_frag, pack_geglu, pack_linear, rest_of, subpixel_conv3x3, to_act, to_planes
+from .weights import Blob, _Pk, _Ref, from_act, pack_conv1x1, pack_device, pack_frag, pack_geglu, pack_linear, subpixel_ups, to_act, to_planes  # noqa: F401  (_Ref: re-exported)
 
 CONFIG_NAME = "config.json"
 SAFETENSORS_NAME = "diffusion_pytorch_model.safetensors"
@@ -55,9 +55,6 @@ _LN_PREFOLD = True
 # per branch on its torch.cat'ed batch).  14 launches run on half (a third) of the rows.
 _SHARE_PREFIX = True
 _F32_CONV_Y = True      # with the f32 residual stream: also the conv output inside FFInflatedConv3d
-# nearest-2x upsample + 3x3 convolution (FFSpatioTempResUpsample3D) as four 2x2 convolutions on the original image, one per output-pixel
-# parity (weights.subpixel_conv3x3): the same function with 4/9 of the multiplies — 0.41 of the step's 5.4 TFLOP become 0.18
-_SUBPIXEL_UPS = os.environ.get("AVSD_SUBPIXEL_UPS", "1") != "0"
 
 
 def _replicate(a: "_Act", r: int) -> "_Act":
@@ -267,13 +264,6 @@ class _Block(nn.Module):
 
 
 # ---- packed (kernel-layout) views ---------------------------------------------------------------------
-class _Pk:
-    """attribute bag of device tensors (views into the packed blob)."""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
-
-
 class _Act:
     """Activation rows [M, C]: `lo` = 16-bit tensor (matrix operand / norm input); `hi` = f32 master of the same values before
     rounding (f32 residual stream) or None.  `res` is what a residual add should read."""
@@ -296,28 +286,17 @@ class _Act:
         return self.hi if self.hi is not None else self.lo
 
 
-class _Ref:
-    """placeholder for item `idx` of the packed blob until the blob exists"""
-
-    def __init__(self, idx: int):
-        self.idx = idx
-
-
 def _per_block(v, n):
     return tuple(v) if isinstance(v, (list, tuple)) else (v,) * n
 
 
-class Packer:
-    """Parameter holders -> kernel-layout tensors, collected into one 256-byte-aligned device blob by `finish`.
+class Packer(Blob):
+    """Parameter holders -> kernel-layout tensors (views into the packed blob, weights.Blob).
     Used by AudioUNet3DConditionModel.pack for the whole model and by the block-level parity tests for single blocks."""
 
     def __init__(self):
-        self.items = []        # packed tensors, on the parameters' device (or meta: layout only)
+        super().__init__()
         self.temb_w, self.temb_b, self.temb_off = [], [], 0
-
-    def reg(self, t: torch.Tensor):
-        self.items.append(t.contiguous())
-        return _Ref(len(self.items) - 1)
 
     def lin(self, m: _Linear):
         return _Pk(w=self.reg(pack_linear(m.weight.float())), b=None if m.bias is None else self.reg(m.bias.detach().float()))
@@ -338,22 +317,24 @@ class Packer:
         x3 = kind is not None and P.three_pass(kind, where)
         x3t = kind is not None and P.three_pass(kind if whole else kind + "_temp", where)
         subpixel = subpixel and m.kernel == 3 and cip % 64 == 0 and cop % 64 == 0       # (the kernel wants whole 64-channel K tiles per tap and whole column tiles per parity)
+        b = torch.zeros(cop, device=w.device)
+        b[:cout] = m.bias.detach().float()
         if m.kernel == 3:
             wf = torch.zeros((cop, 3, 3, cip), dtype=torch.float32, device=w.device)
             wf[:cout, :, :, :cin] = w.permute(0, 2, 3, 1)
-            # an upsampler's convolution: [4 cop, 4 cip], one 2x2 kernel per output-pixel parity (the bias repeats per parity below)
-            wf = subpixel_conv3x3(wf) if subpixel else wf.reshape(cop, 9 * cip)
+            if subpixel:       # an upsampler's convolution: [4 cop, 4 cip], one 2x2 kernel (and one copy of the bias) per output-pixel parity
+                wf, b = subpixel_ups(wf, b)
+            else:
+                wf = wf.reshape(cop, 9 * cip)
         else:
             wf = torch.zeros(cop, cip, device=w.device)
             wf[:cout, :cin] = w.reshape(cout, cin)
-        b = torch.zeros(cop, device=w.device)
-        b[:cout] = m.bias.detach().float()
         wt = torch.zeros(cop, 3, cop, device=w.device)
         wt[:cout, :, :cout] = m.conv_temp.weight.detach().float().reshape(cout, 3, cout)
         wt = wt.reshape(cop, 3 * cop)
         bt = torch.zeros(cop, device=w.device)
         bt[:cout] = m.conv_temp.bias.detach().float()
-        p = _Pk(b=reg(b.repeat(4) if subpixel else b), bt=reg(bt), cout=cop, cin=cip, k=m.kernel, w_r=None, wt_r=None, subpixel=subpixel)
+        p = _Pk(b=reg(b), bt=reg(bt), cout=cop, cin=cip, k=m.kernel, w_r=None, wt_r=None, subpixel=subpixel)
         if x3:
             wm, wr = to_planes(wf)
             p.w, p.w_r = reg(wm), reg(wr)
@@ -442,7 +423,7 @@ class Packer:
         return _Pk(resnets=[self.res(r, where) for r in m.resnets],
                    attentions=[self.tr(a) for a in m.attentions] if hasattr(m, "attentions") else None,
                    down=self.ffconv(m.downsamplers[0].conv, "sampler", where) if hasattr(m, "downsamplers") else None,
-                   up=self.ffconv(m.upsamplers[0].conv, "sampler", where, subpixel=_SUBPIXEL_UPS) if hasattr(m, "upsamplers") else None)
+                   up=self.ffconv(m.upsamplers[0].conv, "sampler", where, subpixel=P.SUBPIXEL_UPS) if hasattr(m, "upsamplers") else None)
 
     def finish(self, pk: _Pk, device, meta: bool = False) -> _Pk:
         """Adds the concatenated time_emb_proj matrix of every ResBlock registered so far, lays all items out in one
@@ -451,44 +432,7 @@ class Packer:
             pk.temb_w = self.reg(pack_linear(torch.cat(self.temb_w, 0)))
             pk.temb_b = self.reg(torch.cat(self.temb_b, 0))
         pk.temb_total = self.temb_off
-        offs, total = [], 0
-        for t in self.items:
-            offs.append(total)
-            total += (t.numel() * t.element_size() + 255) // 256 * 256
-        # split precision: the blob is a twin allocation like every split tensor — the rest plane of item i sits at the
-        # same offset in the second half, so every view below carries it along (precision.py)
-        blob = torch.zeros(total * (2 if P.SPLIT else 1), dtype=torch.uint8, device=device)
-        if not meta:   # meta parameters: layout only — the bytes arrive by broadcast (asva_amd.dist)
-            for t, o in zip(self.items, offs):
-                nb = t.numel() * t.element_size()
-                blob[o:o + nb].copy_(t.reshape(-1).view(torch.uint8))
-                if P.SPLIT and t.dtype == P.ACT:
-                    if not is_twin(t):
-                        raise RuntimeError("split-precision packing: a 16-bit item was not produced by weights.to_act")
-                    blob[total + o:total + o + nb].copy_(rest_of(t).reshape(-1).view(torch.uint8))
-        views = []
-        for t, o in zip(self.items, offs):
-            nb = t.numel() * t.element_size()
-            views.append(blob[o:o + nb].view(t.dtype).view(t.shape))
-
-        def resolve(obj):
-            if isinstance(obj, _Pk):
-                for k, v in list(obj.__dict__.items()):
-                    if isinstance(v, _Ref):
-                        obj.__dict__[k] = views[v.idx]
-                    else:
-                        resolve(v)
-            elif isinstance(obj, list):
-                for v in obj:
-                    resolve(v)
-
-        resolve(pk)
-        pk.blob = blob
-        pk.act_dtype = P.ACT
-        pk.split = P.SPLIT
-        pk.plan = P.plan_key()
-        pk.subpixel = _SUBPIXEL_UPS
-        return pk
+        return super().finish(pk, device, meta)
 
 
 class AudioUNet3DConditionModel(nn.Module):
@@ -756,20 +700,10 @@ class AudioUNet3DConditionModel(nn.Module):
     def pack(self, device: Optional[torch.device] = None):
         """state_dict -> kernel layouts inside ONE device blob (so multi-GPU start-up is a single RCCL
         broadcast, see asva_amd.dist).  Returns the structure of typed views."""
-        if device is not None:
-            device = torch.device(device)
-            if device.type == "cuda" and device.index is None:
-                device = torch.device("cuda", torch.cuda.current_device())
-        if (self._packed is not None and self._packed.act_dtype == P.ACT and getattr(self._packed, "split", False) == P.SPLIT
-                and getattr(self._packed, "plan", None) == P.plan_key() and getattr(self._packed, "subpixel", None) == _SUBPIXEL_UPS
-                and (device is None or self._packed.blob.device == device)):
+        device = pack_device(device)
+        if self._packed is not None and self._packed.key == P.pack_key() and (device is None or self._packed.blob.device == device):
             return self._packed
-        device = device if device is not None else self.device
-        if device.type == "meta":
-            raise RuntimeError("pack: pass the target device explicitly for a meta-initialised model")
-        if device.type != "cuda" and not getattr(ops, "EMULATED", False):   # EMULATED: tests/emu_ops.py seam
-            raise RuntimeError("AudioUNet3DConditionModel.pack: the MI355X path needs a cuda (HIP) device; "
-                               "move the model with .to('cuda') first — there is no CPU compute path")
+        device = pack_device(device, self.device, ops, "AudioUNet3DConditionModel.pack")
         pr = Packer()
         pk = _Pk(conv_in=pr.ffconv(self.conv_in, "conv_in"), t1=pr.lin(self.time_embedding.linear_1), t2=pr.lin(self.time_embedding.linear_2),
                  down=[pr.block(b, f"down_blocks.{i}") for i, b in enumerate(self.down_blocks)], mid=pr.block(self.mid_block, "mid_block"),

@@ -24,8 +24,8 @@ from . import precision as P
 from torch import nn
 
 from . import ops
-from .unet import FrozenConfig, _Affine, _Conv, _Linear, _Pk, _Ref
-from .weights import is_twin, pack_conv1x1, pack_conv3x3, pack_linear, rest_of, subpixel_conv3x3, to_act
+from .unet import FrozenConfig, _Affine, _Conv, _Linear
+from .weights import Blob, _Pk, pack_conv1x1, pack_conv3x3, pack_device, pack_linear, subpixel_ups, to_act
 
 
 class DecoderOutput:
@@ -148,9 +148,6 @@ class _Decoder(nn.Module):
 
 
 # older diffusers checkpoints name the mid-block attention projections differently
-# the upsamplers' nearest-2x + 3x3 convolution as four per-parity 2x2 convolutions on the original image (weights.subpixel_conv3x3): 2.09 of
-# the decoder's 7.47 TFLOP per 12 x 256 x 256 clip become 0.93
-_SUBPIXEL_UPS = os.environ.get("AVSD_SUBPIXEL_UPS", "1") != "0"
 _LEGACY_ATTN = {"query": "to_q", "key": "to_k", "value": "to_v", "proj_attn": "to_out.0"}
 
 
@@ -274,21 +271,12 @@ class AutoencoderKL(nn.Module):
 
     # ---- packing -----------------------------------------------------------------------------------------------
     def pack(self, device=None):
-        if device is not None:
-            device = torch.device(device)
-            if device.type == "cuda" and device.index is None:
-                device = torch.device("cuda", torch.cuda.current_device())
-        if (self._packed is not None and (device is None or self._packed.blob.device == device)
-                and getattr(self._packed, "split", False) == P.SPLIT and getattr(self._packed, "act_dtype", P.ACT) == P.ACT):
+        device = pack_device(device)
+        if self._packed is not None and self._packed.key == P.pack_key() and (device is None or self._packed.blob.device == device):
             return self._packed
-        device = device if device is not None else self.device
-        if device.type != "cuda" and not getattr(ops, "EMULATED", False):
-            raise RuntimeError("AutoencoderKL.pack: the MI355X path needs a cuda (HIP) device — there is no CPU compute path")
-        items = []
-
-        def reg(t):
-            items.append(t.contiguous())
-            return _Ref(len(items) - 1)
+        device = pack_device(device, self.device, ops, "AutoencoderKL.pack")
+        blob = Blob()
+        reg = blob.reg
 
         def aff(m):
             return _Pk(g=reg(m.weight.detach().float()), b=reg(m.bias.detach().float()))
@@ -305,10 +293,10 @@ class AutoencoderKL(nn.Module):
             kernels on the original image, 4/9 of the multiplies (weights.subpixel_conv3x3; AVSD_GEMM_CONV3 with ups = 2) — where the
             kernel's layout rules hold (whole 64-channel K tiles per tap, whole column tiles per parity)"""
             cout, cin = m.weight.shape[:2]
-            if not _SUBPIXEL_UPS or cout % 64 or cin % 64:
+            if not P.SUBPIXEL_UPS or cout % 64 or cin % 64:
                 return conv3(m)
-            wf = m.weight.detach().float().permute(0, 2, 3, 1).contiguous()
-            return _Pk(w=reg(to_act(subpixel_conv3x3(wf))), b=reg(m.bias.detach().float().repeat(4)), cout=cout, subpixel=True)
+            wf, b = subpixel_ups(m.weight.detach().float().permute(0, 2, 3, 1).contiguous(), m.bias.detach().float())
+            return _Pk(w=reg(to_act(wf)), b=reg(b), cout=cout, subpixel=True)
 
         def conv1(m):
             cout, cin = m.weight.shape[:2]
@@ -346,40 +334,8 @@ class AutoencoderKL(nn.Module):
                  up=[_Pk(resnets=[res(r) for r in u.resnets],
                          up=conv3_up(u.upsamplers[0].conv) if hasattr(u, "upsamplers") else None) for u in d.up_blocks],
                  norm_out=aff(d.conv_norm_out), conv_out=conv3(d.conv_out))
-        offs, total = [], 0
-        for t in items:
-            offs.append(total)
-            total += (t.numel() * t.element_size() + 255) // 256 * 256
-        # split precision: a twin blob, the rest plane of every 16-bit item at the same offset in the second half (precision.py)
-        blob = torch.zeros(total * (2 if P.SPLIT else 1), dtype=torch.uint8, device=device)
-        views = []
-        for t, o in zip(items, offs):
-            nb = t.numel() * t.element_size()
-            if not t.is_meta:
-                blob[o:o + nb].copy_(t.reshape(-1).view(torch.uint8))
-                if P.SPLIT and t.dtype == P.ACT:
-                    if not is_twin(t):
-                        raise RuntimeError("split-precision packing: a 16-bit item was not produced by weights.to_act")
-                    blob[total + o:total + o + nb].copy_(rest_of(t).reshape(-1).view(torch.uint8))
-            views.append(blob[o:o + nb].view(t.dtype).view(t.shape))
-
-        def resolve(obj):
-            if isinstance(obj, _Pk):
-                for k, v in list(obj.__dict__.items()):
-                    if isinstance(v, _Ref):
-                        obj.__dict__[k] = views[v.idx]
-                    else:
-                        resolve(v)
-            elif isinstance(obj, list):
-                for v in obj:
-                    resolve(v)
-
-        resolve(pk)
-        pk.blob = blob
-        pk.split = P.SPLIT
-        pk.act_dtype = P.ACT
-        self._packed = pk
-        return pk
+        self._packed = blob.finish(pk, device, meta=next(self.parameters()).is_meta)
+        return self._packed
 
     # ---- decode ----------------------------------------------------------------------------------------------------
     @torch.no_grad()

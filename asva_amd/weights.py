@@ -106,6 +106,13 @@ def subpixel_conv3x3(wf: torch.Tensor) -> torch.Tensor:
     return out.reshape(4 * cout, 4 * cin)
 
 
+def subpixel_ups(wf: torch.Tensor, b: torch.Tensor):
+    """an upsampler's 3x3 convolution and bias in the sub-pixel form: wf [cout, 3, 3, cin] f32, b [cout] -> the [4 cout, 4 cin] matrix
+    of subpixel_conv3x3 and the bias once per output-pixel parity.  Padding and the kernel's layout rule (whole 64-channel K tiles per
+    tap, whole column tiles per parity) are the caller's: the UNet tests its padded channel counts, the VAE the checkpoint's"""
+    return subpixel_conv3x3(wf), b.repeat(4)
+
+
 def geglu_row_order(nh: int) -> torch.Tensor:
     """Packed row r of a GEGLU projection with nh output features reads source row order[r]."""
     assert nh % 16 == 0, "GEGLU packing needs the inner dim to be a multiple of 16"
@@ -137,3 +144,87 @@ def pad_rows(w: torch.Tensor, mult: int = 4) -> torch.Tensor:
         return w
     pad = torch.zeros((mult - n % mult,) + tuple(w.shape[1:]), dtype=w.dtype, device=w.device)
     return torch.cat([w, pad], 0).contiguous()
+
+
+# ---- the packed blob -------------------------------------------------------------------------------------------------------------
+class _Pk:
+    """attribute bag of device tensors (views into the packed blob)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+class _Ref:
+    """placeholder for item `idx` of the packed blob until the blob exists"""
+
+    def __init__(self, idx: int):
+        self.idx = idx
+
+
+class Blob:
+    """Kernel-layout tensors of one model, collected by `reg` and laid out in ONE 256-byte-aligned device blob by `finish`: the unit
+    the multi-GPU start-up broadcasts (asva_amd.dist) and the launch-plan export ships as a CONST region (asva_amd.plan)."""
+
+    def __init__(self):
+        self.items = []        # packed tensors, on the parameters' device (or meta: layout only)
+
+    def reg(self, t: torch.Tensor) -> _Ref:
+        self.items.append(t.contiguous())
+        return _Ref(len(self.items) - 1)
+
+    def finish(self, root: _Pk, device, meta: bool = False) -> _Pk:
+        """lays all items out in one blob on `device`, replaces the placeholders inside `root` by typed views of it and stamps
+        `root` with the blob and the precision.pack_key() it was packed under"""
+        offs, total = [], 0
+        for t in self.items:
+            offs.append(total)
+            total += (t.numel() * t.element_size() + 255) // 256 * 256
+        # split precision: the blob is a twin allocation like every split tensor — the rest plane of item i sits at the
+        # same offset in the second half, so every view below carries it along (precision.py)
+        blob = torch.zeros(total * (2 if P.SPLIT else 1), dtype=torch.uint8, device=device)
+        views = []
+        for t, o in zip(self.items, offs):
+            nb = t.numel() * t.element_size()
+            if not meta:   # meta parameters: layout only — the bytes arrive by broadcast (asva_amd.dist)
+                blob[o:o + nb].copy_(t.reshape(-1).view(torch.uint8))
+                if P.SPLIT and t.dtype == P.ACT:
+                    if not is_twin(t):
+                        raise RuntimeError("split-precision packing: a 16-bit item was not produced by weights.to_act")
+                    blob[total + o:total + o + nb].copy_(rest_of(t).reshape(-1).view(torch.uint8))
+            views.append(blob[o:o + nb].view(t.dtype).view(t.shape))
+
+        def resolve(obj):
+            if isinstance(obj, _Pk):
+                for k, v in list(obj.__dict__.items()):
+                    if isinstance(v, _Ref):
+                        obj.__dict__[k] = views[v.idx]
+                    else:
+                        resolve(v)
+            elif isinstance(obj, list):
+                for v in obj:
+                    resolve(v)
+
+        resolve(root)
+        root.blob = blob
+        root.key = P.pack_key()
+        root.split = P.SPLIT
+        return root
+
+
+def pack_device(device, own=None, ops=None, who="pack"):
+    """pack()'s device argument, normalised for its cache test: "cuda" is the current device, None (any device) stays None.  Called again
+    with the model's `own` device (it stands in for None) and kernel module once pack() has to pack: the kernels must be able to
+    read the result (ops.EMULATED: tests/emu_ops.py seam)."""
+    if device is not None:
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+    if own is None:
+        return device
+    device = own if device is None else device
+    if device.type == "meta":
+        raise RuntimeError(f"{who}: pass the target device explicitly for a meta-initialised model")
+    if device.type != "cuda" and not getattr(ops, "EMULATED", False):
+        raise RuntimeError(f"{who}: the MI355X path needs a cuda (HIP) device; move the model with .to('cuda') first — "
+                           "there is no CPU compute path")
+    return device

@@ -586,6 +586,55 @@ def test_meta_replica_packs_the_same_blob_layout(mode):
         U.ops = old_ops
 
 
+@pytest.mark.parametrize("mode", ["bf16", "fp16", "split", "plan"])
+def test_packed_blob_layout_is_pinned(mode):
+    """The packed blob is what the multi-GPU start-up broadcasts (asva_amd.dist) and the launch-plan export ships as a CONST region
+    (asva_amd.plan): its byte length and the (attribute path, dtype, shape, byte offset) of every view, for the tiny UNet (padded 3x3
+    upsamplers) and a small VAE (sub-pixel upsampler), are recorded in tests/golden/pack_layout.json by oracle/gen_pack_layout.py, whose
+    tree walk and digest this test shares.  A change that needs a new recording to pass has moved the layout."""
+    from oracle import gen_pack_layout as G
+
+    want = load_shapes("pack_layout.json")
+    try:
+        G.set_mode(mode)
+        for which in G.MODELS:
+            pk = G.pack_cpu(G.build_model(which))
+            assert [b.up.subpixel for b in pk.up if b.up is not None] == ([False] * 3 if which == "unet" else [True]), which
+            assert G.layout_record(pk) == want[which][mode], which
+    finally:
+        G.set_mode(None)
+
+
+@pytest.mark.parametrize("which", ["unet", "vae"])
+def test_pack_cache_is_keyed_on_every_process_wide_switch(which):
+    """pack() keeps its copy while precision.pack_key() and the device stay the same; flipping the storage type, split precision, the
+    per-layer plan or the sub-pixel flag packs a new object, and flipping back packs the first blob again, byte for byte."""
+    from asva_amd import precision as P
+    from oracle import gen_pack_layout as G
+
+    def subpixel(on):
+        P.SUBPIXEL_UPS = on
+
+    m = G.build_model(which)
+    was = P.SUBPIXEL_UPS
+    try:
+        first = G.pack_cpu(m)
+        assert G.pack_cpu(m) is first
+        blob0 = first.blob.clone()
+        for flip, back in ((lambda: P.set_precision("fp16"), lambda: P.set_precision("bf16")), (lambda: P.set_split(True), lambda: P.set_split(False)),
+                           (lambda: P.set_plan(True), lambda: P.set_plan(False)), (lambda: subpixel(not was), lambda: subpixel(was))):
+            before = G.pack_cpu(m)
+            flip()
+            other = G.pack_cpu(m)
+            assert other is not before and G.pack_cpu(m) is other
+            back()
+            again = G.pack_cpu(m)
+            assert again is not other and again is not before and torch.equal(again.blob, blob0)
+    finally:
+        G.set_mode(None)
+        subpixel(was)
+
+
 @pytest.mark.parametrize("hs,ws", [(4, 4), (3, 5)])
 def test_subpixel_upsample_conv_packing_is_the_same_function(hs, ws):
     """weights.subpixel_conv3x3: nearest-2x upsample + 3x3 pad-1 convolution (FFSpatioTempResUpsample3D, ff_spatio_temp_resnet_3d.py:48-55)
