@@ -131,6 +131,12 @@ SIGNATURES = {
     "avsd_vae_postprocess_x2": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int, c_void_p]),
     "avsd_vae_postprocess_u8_x2": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int, c_void_p]),
     "avsd_gemm_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    # AVSync scorer (csrc/avsync.hip): f32 in both builds
+    "avsd_convnd_f32": (c_int, [c_void_p] * 6 + [c_int] * 20 + [c_void_p]),
+    "avsd_maxpool_hw_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "avsd_mean_rows_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "avsd_resize_aa_normalize_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                             c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_float] * 6 + [c_void_p]),
     # launch plans (asva_amd/plan.py records them; any host replays them)
     "avsd_plan_bundle_load": (c_int, [C.c_char_p, C.POINTER(c_void_p)]),
     "avsd_plan_bundle_free": (None, [c_void_p]),

@@ -1,0 +1,337 @@
+// AVSync scorer (asva_amd/avsync.py): the kernels of the reference's evaluation classifier — an R(2+1)D-18 video network, a 2-D
+// convolutional audio network on the log-mel spectrogram and a 3-layer FC head (avsync/models/{video,audio,head}.py), and the video
+// preprocessing of avgen/evaluations/avsync/compute_avsync.py:14-34.  A metric must not move with the storage mode of what it
+// measures, so NOTHING here uses the 16-bit type of the build: tensors are f32, products run on the f32-input matrix cores
+// (v_mfma_f32_32x32x2_f32, as csrc/gemm_f32.hip), and the bf16 and fp16 libraries compile this file to the same arithmetic.
+//
+// Layout: channels-last f32, video activations [n][t][h][w][c], audio activations the same with t = 1.
+#include "avsd_common.h"
+
+namespace {
+
+// ---- avsd_convnd_f32 -------------------------------------------------------------------------------------------------------------
+// Implicit GEMM: row m = (n, to, ho, wo), column = output channel, K = taps * cin (tap-major, cin-minor), gathered from the input
+// inside the kernel.  Tile (64 FM) x (64 FN) x 32, 256 threads = 2 x 2 waves, each wave FM x FN accumulator fragments of 32 x 32;
+// LDS rows padded to 33 floats as in gemm_f32.hip.  The next K tile is fetched into registers while the matrix cores work on the
+// current one.  Every output element is one k-ordered chain 0 .. K-1 whatever the tile and whatever its row index: results do not
+// depend on the tile choice or on the batch size.
+constexpr int CK = 32, CP = CK + 1;
+
+struct ConvGeom {
+  int n, ti, hi, wi, cin, to, ho, wo, cout;
+  int kt, kh, kw, st, sh, sw, pt, ph, pw;
+  int ldw, relu, M, K;
+};
+
+template <int FM, int FN, bool VEC>
+__global__ __launch_bounds__(256) void convnd_f32_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                         const float* __restrict__ bias, const float* __restrict__ res,
+                                                         const float* __restrict__ rscale, float* __restrict__ out, ConvGeom g) {
+  constexpr int BM = 64 * FM, BN = 64 * FN;
+  constexpr int NA = VEC ? BM / 32 : BM / 8;      // A elements (float4 / float) each thread fetches per K tile
+  constexpr int NW = VEC ? BN / 32 : BN / 8;
+  __shared__ float sA[BM * CP];
+  __shared__ float sW[BN * CP];
+  __shared__ int4 sRow[BM];                        // per tile row: (sample n, to*st - pt, ho*sh - ph, wo*sw - pw)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave & 1, wn = wave >> 1;
+  const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
+  const int M = g.M, K = g.K;
+
+  for (int r = tid; r < BM; r += 256) {
+    const int m = m0 + r;
+    int4 v = make_int4(0, -(1 << 28), 0, 0);       // rows past M: every tap falls outside the input -> zeros
+    if (m < M) {
+      int q = m;
+      const int wo = q % g.wo; q /= g.wo;
+      const int ho = q % g.ho; q /= g.ho;
+      const int to = q % g.to; q /= g.to;
+      v = make_int4(q, to * g.st - g.pt, ho * g.sh - g.ph, wo * g.sw - g.pw);
+    }
+    sRow[r] = v;
+  }
+  __syncthreads();
+
+  f32x16 acc[FM][FN];
+#pragma unroll
+  for (int a = 0; a < FM; ++a)
+#pragma unroll
+    for (int b = 0; b < FN; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+
+  // VEC (cin % 32 == 0, so a K tile lies inside one tap): thread = (row lr of a 32-row slab, float4 at channel lk)
+  // else: thread = (k column tid & 31, row tid >> 5 of an 8-row slab), one float at a time, tap decoded per element
+  const int lr = VEC ? tid >> 3 : tid >> 5;
+  const int lk = VEC ? (tid & 7) * 4 : tid & 31;
+  float4 ra[VEC ? NA : 1], rw[VEC ? NW : 1];
+  float fa[VEC ? 1 : NA], fw[VEC ? 1 : NW];
+
+  auto fetch = [&](int k0) {
+    if constexpr (VEC) {
+      const int tap = k0 / g.cin, c = k0 - tap * g.cin + lk;
+      const int dw = tap % g.kw, dh = (tap / g.kw) % g.kh, dt = tap / (g.kw * g.kh);
+#pragma unroll
+      for (int i = 0; i < NA; ++i) {
+        const int4 rv = sRow[lr + 32 * i];
+        const int t = rv.y + dt, h = rv.z + dh, ww = rv.w + dw;
+        const bool ok = (unsigned)t < (unsigned)g.ti && (unsigned)h < (unsigned)g.hi && (unsigned)ww < (unsigned)g.wi;
+        ra[i] = ok ? *reinterpret_cast<const float4*>(x + ((((int64_t)rv.x * g.ti + t) * g.hi + h) * g.wi + ww) * g.cin + c)
+                   : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+#pragma unroll
+      for (int i = 0; i < NW; ++i) {
+        const int nn = n0 + lr + 32 * i;
+        rw[i] = nn < g.cout ? *reinterpret_cast<const float4*>(w + (int64_t)nn * g.ldw + k0 + lk) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    } else {
+      const int k = k0 + lk;
+      const bool kok = k < K;
+      const int tap = k / g.cin, c = k - tap * g.cin;
+      const int dw = tap % g.kw, dh = (tap / g.kw) % g.kh, dt = tap / (g.kw * g.kh);
+#pragma unroll
+      for (int i = 0; i < NA; ++i) {
+        const int4 rv = sRow[lr + 8 * i];
+        const int t = rv.y + dt, h = rv.z + dh, ww = rv.w + dw;
+        const bool ok = kok && (unsigned)t < (unsigned)g.ti && (unsigned)h < (unsigned)g.hi && (unsigned)ww < (unsigned)g.wi;
+        fa[i] = ok ? x[((((int64_t)rv.x * g.ti + t) * g.hi + h) * g.wi + ww) * g.cin + c] : 0.f;
+      }
+#pragma unroll
+      for (int i = 0; i < NW; ++i) {
+        const int nn = n0 + lr + 8 * i;
+        fw[i] = (kok && nn < g.cout) ? w[(int64_t)nn * g.ldw + k] : 0.f;
+      }
+    }
+  };
+  auto stage = [&]() {
+    if constexpr (VEC) {
+#pragma unroll
+      for (int i = 0; i < NA; ++i) {
+        float* d = sA + (lr + 32 * i) * CP + lk;
+        d[0] = ra[i].x; d[1] = ra[i].y; d[2] = ra[i].z; d[3] = ra[i].w;
+      }
+#pragma unroll
+      for (int i = 0; i < NW; ++i) {
+        float* d = sW + (lr + 32 * i) * CP + lk;
+        d[0] = rw[i].x; d[1] = rw[i].y; d[2] = rw[i].z; d[3] = rw[i].w;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < NA; ++i) sA[(lr + 8 * i) * CP + lk] = fa[i];
+#pragma unroll
+      for (int i = 0; i < NW; ++i) sW[(lr + 8 * i) * CP + lk] = fw[i];
+    }
+  };
+
+  fetch(0);
+  for (int k0 = 0; k0 < K; k0 += CK) {
+    __syncthreads();                  // everybody is done reading the previous tile
+    stage();
+    __syncthreads();
+    if (k0 + CK < K) fetch(k0 + CK);
+    // operand layout of v_mfma_f32_32x32x2_f32: A[i = lane & 31][k = lane >> 5], B[k = lane >> 5][j = lane & 31]
+    const float* pa = sA + (wm * 32 * FM + (lane & 31)) * CP + (lane >> 5);
+    const float* pw = sW + (wn * 32 * FN + (lane & 31)) * CP + (lane >> 5);
+#pragma unroll
+    for (int kk = 0; kk < CK; kk += 2) {
+      float av[FM], wv[FN];
+#pragma unroll
+      for (int a = 0; a < FM; ++a) av[a] = pa[a * 32 * CP + kk];
+#pragma unroll
+      for (int b = 0; b < FN; ++b) wv[b] = pw[b * 32 * CP + kk];
+#pragma unroll
+      for (int a = 0; a < FM; ++a)
+#pragma unroll
+        for (int b = 0; b < FN; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a], wv[b], acc[a][b], 0, 0, 0);
+    }
+  }
+  // C/D layout: column j = lane & 31 (n), row i = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) (m)
+#pragma unroll
+  for (int a = 0; a < FM; ++a)
+#pragma unroll
+    for (int b = 0; b < FN; ++b) {
+      const int nn = n0 + wn * 32 * FN + b * 32 + (lane & 31);
+      if (nn >= g.cout) continue;
+      const float bv = bias ? bias[nn] : 0.f;
+      const float rs = rscale ? rscale[nn] : 1.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = m0 + wm * 32 * FM + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (m >= M) continue;
+        float v = acc[a][b][r] + bv;
+        if (res) v += rs * res[(int64_t)m * g.cout + nn];
+        if (g.relu) v = fmaxf(v, 0.f);
+        out[(int64_t)m * g.cout + nn] = v;
+      }
+    }
+}
+
+template <int FM, int FN>
+void launch_conv(bool vec, dim3 grid, hipStream_t s, const float* x, const float* w, const float* bias, const float* res,
+                 const float* rscale, float* out, const ConvGeom& g) {
+  if (vec) hipLaunchKernelGGL((convnd_f32_kernel<FM, FN, true>), grid, dim3(256), 0, s, x, w, bias, res, rscale, out, g);
+  else hipLaunchKernelGGL((convnd_f32_kernel<FM, FN, false>), grid, dim3(256), 0, s, x, w, bias, res, rscale, out, g);
+}
+
+// ---- avsd_maxpool_hw_f32: (1, 3, 3) window, stride (1, 2, 2), padding (0, 1, 1); one thread per output pixel and 4 channels ---------
+__global__ __launch_bounds__(256) void maxpool_hw_f32_kernel(const float* __restrict__ x, float* __restrict__ out, int hi, int wi,
+                                                             int c4, int ho, int wo, int64_t total) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int c = (int)(idx % c4);
+  int64_t q = idx / c4;
+  const int ox = (int)(q % wo); q /= wo;
+  const int oy = (int)(q % ho);
+  const int64_t img = q / ho;
+  const float4* src = reinterpret_cast<const float4*>(x) + img * hi * wi * c4 + c;
+  float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);   // padded positions do not take part
+#pragma unroll
+  for (int dy = 0; dy < 3; ++dy) {
+    const int y = 2 * oy - 1 + dy;
+    if ((unsigned)y >= (unsigned)hi) continue;
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx) {
+      const int xx = 2 * ox - 1 + dx;
+      if ((unsigned)xx >= (unsigned)wi) continue;
+      const float4 v = src[((int64_t)y * wi + xx) * c4];
+      m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+    }
+  }
+  reinterpret_cast<float4*>(out)[idx] = m;
+}
+
+// ---- avsd_mean_rows_f32: x [n][rows][c] -> out [n][c].  Thread (channel, quarter q): rows q, q + 4, ... in order, accumulated in
+// double so that a long column costs no accuracy; the four partial sums are combined in a fixed order.  No atomics. --------------------
+__global__ __launch_bounds__(256) void mean_rows_f32_kernel(const float* __restrict__ x, float* __restrict__ out, int rows, int c) {
+  __shared__ double part[4][64];
+  const int cl = threadIdx.x & 63, q = threadIdx.x >> 6;
+  const int ch = blockIdx.x * 64 + cl;
+  const float* src = x + (int64_t)blockIdx.y * rows * c;
+  double s = 0.0;
+  if (ch < c)
+    for (int r = q; r < rows; r += 4) s += (double)src[(int64_t)r * c + ch];
+  part[q][cl] = s;
+  __syncthreads();
+  if (q == 0 && ch < c)
+    out[(int64_t)blockIdx.y * c + ch] = (float)(((part[0][cl] + part[1][cl]) + (part[2][cl] + part[3][cl])) / (double)rows);
+}
+
+// ---- avsd_resize_aa_normalize_f32: separable antialiased resampling with host-built taps, horizontal pass then vertical ------------
+// pass 1: x [img*3][hi][wi] -> tmp [img*3][hi][wo]
+__global__ __launch_bounds__(256) void resize_h_f32_kernel(const float* __restrict__ x, float* __restrict__ tmp,
+                                                           const int* __restrict__ xs, const int* __restrict__ xn,
+                                                           const float* __restrict__ xw, int taps, int wi, int wo, int64_t total) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int ox = (int)(idx % wo);
+  const int64_t row = idx / wo;
+  const int n = min(max(xn[ox], 0), taps);                     // taps <= wi (checked): a corrupt table cannot leave the row
+  const float* src = x + row * wi + min(max(xs[ox], 0), wi - n);
+  const float* wt = xw + (int64_t)ox * taps;
+  float s = 0.f;
+  for (int j = 0; j < n; ++j) s += src[j] * wt[j];
+  tmp[idx] = s;
+}
+// pass 2: tmp -> out [img][ho][wo][3] = (value - mean[c]) / std[c]
+__global__ __launch_bounds__(256) void resize_v_norm_f32_kernel(const float* __restrict__ tmp, float* __restrict__ out,
+                                                                const int* __restrict__ ys, const int* __restrict__ yn,
+                                                                const float* __restrict__ yw, int taps, int hi, int ho, int wo,
+                                                                float m0, float m1, float m2, float s0, float s1, float s2,
+                                                                int64_t total) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int ox = (int)(idx % wo);
+  int64_t q = idx / wo;
+  const int oy = (int)(q % ho); q /= ho;
+  const int c = (int)(q % 3);
+  const int64_t img = q / 3;
+  const int n = min(max(yn[oy], 0), taps);
+  const float* src = tmp + ((img * 3 + c) * hi + min(max(ys[oy], 0), hi - n)) * wo + ox;
+  const float* wt = yw + (int64_t)oy * taps;
+  float s = 0.f;
+  for (int j = 0; j < n; ++j) s += src[(int64_t)j * wo] * wt[j];
+  const float mean = c == 0 ? m0 : c == 1 ? m1 : m2, sd = c == 0 ? s0 : c == 1 ? s1 : s2;
+  out[((img * ho + oy) * wo + ox) * 3 + c] = (s - mean) / sd;
+}
+
+}  // namespace
+
+extern "C" int avsd_convnd_f32(const float* x, const float* w, const float* bias, const float* res, const float* rscale, float* out,
+                               int n, int ti, int hi, int wi, int cin, int to, int ho, int wo, int cout, int kt, int kh, int kw,
+                               int st, int sh, int sw, int pt, int ph, int pw, int ldw, int relu, void* stream) {
+  AVSD_REQUIRE(x && w && out, "convnd_f32: null pointer");
+  AVSD_REQUIRE(n > 0 && ti > 0 && hi > 0 && wi > 0 && cin > 0 && cout > 0, "convnd_f32: sizes must be positive");
+  AVSD_REQUIRE(kt > 0 && kh > 0 && kw > 0 && kt <= 16 && kh <= 16 && kw <= 16 && st > 0 && sh > 0 && sw > 0,
+               "convnd_f32: taps must be 1 .. 16 and strides positive");
+  AVSD_REQUIRE(pt >= 0 && ph >= 0 && pw >= 0 && pt < kt && ph < kh && pw < kw, "convnd_f32: padding must be smaller than the window");
+  AVSD_REQUIRE(ti + 2 * pt >= kt && hi + 2 * ph >= kh && wi + 2 * pw >= kw, "convnd_f32: the window does not fit the padded input");
+  AVSD_REQUIRE(to == (ti + 2 * pt - kt) / st + 1 && ho == (hi + 2 * ph - kh) / sh + 1 && wo == (wi + 2 * pw - kw) / sw + 1,
+               "convnd_f32: output size (%d, %d, %d) does not follow from input (%d, %d, %d), window, stride and padding", to, ho, wo,
+               ti, hi, wi);
+  const int64_t K64 = (int64_t)kt * kh * kw * cin, M64 = (int64_t)n * to * ho * wo;
+  AVSD_REQUIRE(ldw >= K64, "convnd_f32: ldw %d is smaller than K = taps * cin = %lld", ldw, (long long)K64);
+  AVSD_REQUIRE(M64 < (1ll << 31) && K64 < (1ll << 24) && (int64_t)n * ti * hi * wi < (1ll << 31), "convnd_f32: tensor too large");
+  AVSD_REQUIRE(!rscale || res, "convnd_f32: rscale without a residual");
+  const bool vec = cin % CK == 0 && ldw % 4 == 0 && ((uintptr_t)x | (uintptr_t)w) % 16 == 0;
+  ConvGeom g{n, ti, hi, wi, cin, to, ho, wo, cout, kt, kh, kw, st, sh, sw, pt, ph, pw, ldw, relu ? 1 : 0, (int)M64, (int)K64};
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  // tile by shape alone (the result does not depend on it): 64 output channels get a 64-wide tile; a layer too small to give
+  // every CU a 128-row tile runs on 64 x 64 tiles
+  const int fn = cout <= 64 ? 1 : 2;
+  const int64_t big = ((M64 + 127) / 128) * ((cout + 64 * fn - 1) / (64 * fn));
+  if (big < 256) {
+    dim3 grid((unsigned)((cout + 63) / 64), (unsigned)((M64 + 63) / 64));
+    launch_conv<1, 1>(vec, grid, s, x, w, bias, res, rscale, out, g);
+  } else if (fn == 1) {
+    dim3 grid((unsigned)((cout + 63) / 64), (unsigned)((M64 + 127) / 128));
+    launch_conv<2, 1>(vec, grid, s, x, w, bias, res, rscale, out, g);
+  } else {
+    dim3 grid((unsigned)((cout + 127) / 128), (unsigned)((M64 + 127) / 128));
+    launch_conv<2, 2>(vec, grid, s, x, w, bias, res, rscale, out, g);
+  }
+  AVSD_CHECK_LAUNCH("convnd_f32 launch");
+  return AVSD_OK;
+}
+
+extern "C" int avsd_maxpool_hw_f32(const float* x, float* out, int n_img, int hi, int wi, int c, int ho, int wo, void* stream) {
+  AVSD_REQUIRE(x && out, "maxpool_hw_f32: null pointer");
+  AVSD_REQUIRE(n_img > 0 && hi > 0 && wi > 0 && c > 0 && c % 4 == 0, "maxpool_hw_f32: sizes must be positive, channels a multiple of 4");
+  AVSD_REQUIRE(ho == (hi - 1) / 2 + 1 && wo == (wi - 1) / 2 + 1, "maxpool_hw_f32: output size (%d, %d) does not follow from input (%d, %d)", ho,
+               wo, hi, wi);
+  AVSD_REQUIRE(((uintptr_t)x | (uintptr_t)out) % 16 == 0, "maxpool_hw_f32: pointers must be 16-byte aligned");
+  const int64_t total = (int64_t)n_img * ho * wo * (c / 4);
+  AVSD_REQUIRE((total + 255) / 256 < (1ll << 31), "maxpool_hw_f32: tensor too large");
+  hipLaunchKernelGGL(maxpool_hw_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x,
+                     out, hi, wi, c / 4, ho, wo, total);
+  AVSD_CHECK_LAUNCH("maxpool_hw_f32 launch");
+  return AVSD_OK;
+}
+
+extern "C" int avsd_mean_rows_f32(const float* x, float* out, int n, int rows, int c, void* stream) {
+  AVSD_REQUIRE(x && out, "mean_rows_f32: null pointer");
+  AVSD_REQUIRE(n > 0 && rows > 0 && c > 0 && n < 65536, "mean_rows_f32: sizes must be positive (n < 65536)");
+  hipLaunchKernelGGL(mean_rows_f32_kernel, dim3((unsigned)((c + 63) / 64), (unsigned)n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     x, out, rows, c);
+  AVSD_CHECK_LAUNCH("mean_rows_f32 launch");
+  return AVSD_OK;
+}
+
+extern "C" int avsd_resize_aa_normalize_f32(const float* x, float* tmp, float* out, int n_img, int hi, int wi, int ho, int wo,
+                                            const int* y_start, const int* y_count, const float* y_weight, int y_taps,
+                                            const int* x_start, const int* x_count, const float* x_weight, int x_taps, int crop,
+                                            float mean0, float mean1, float mean2, float std0, float std1, float std2, void* stream) {
+  AVSD_REQUIRE(x && tmp && out && y_start && y_count && y_weight && x_start && x_count && x_weight, "resize_aa_normalize_f32: null pointer");
+  AVSD_REQUIRE(n_img > 0 && hi > 0 && wi > 0 && ho > 0 && wo > 0 && y_taps > 0 && x_taps > 0 && y_taps <= hi && x_taps <= wi,
+               "resize_aa_normalize_f32: sizes must be positive, taps no more than the input size");
+  AVSD_REQUIRE(crop == ho && crop == wo, "resize_aa_normalize_f32: the centre crop (%d) must equal the resized size (%d, %d)", crop, ho, wo);
+  AVSD_REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, "resize_aa_normalize_f32: std must not be zero");
+  const int64_t t1 = (int64_t)n_img * 3 * hi * wo, t2 = (int64_t)n_img * 3 * ho * wo;
+  AVSD_REQUIRE((t1 + 255) / 256 < (1ll << 31) && (t2 + 255) / 256 < (1ll << 31), "resize_aa_normalize_f32: tensor too large");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(resize_h_f32_kernel, dim3((unsigned)((t1 + 255) / 256)), dim3(256), 0, s, x, tmp, x_start, x_count, x_weight, x_taps, wi,
+                     wo, t1);
+  hipLaunchKernelGGL(resize_v_norm_f32_kernel, dim3((unsigned)((t2 + 255) / 256)), dim3(256), 0, s, tmp, out, y_start, y_count, y_weight,
+                     y_taps, hi, ho, wo, mean0, mean1, mean2, std0, std1, std2, t2);
+  AVSD_CHECK_LAUNCH("resize_aa_normalize_f32 launch");
+  return AVSD_OK;
+}

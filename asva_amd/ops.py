@@ -1296,3 +1296,73 @@ def vit_tokens(patches: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, b: i
     out = torch.empty((b * (1 + n_p + tail_rows), Cc), dtype=P.ACT, device=patches.device)
     check(_lib.lib().avsd_vit_tokens(_p(patches), _p(cls), _p(pos), _p(out), b, n_p, Cc, tail_rows, _stream()), "avsd_vit_tokens")
     return out
+
+
+# ---- AVSync scorer (csrc/avsync.hip): f32 tensors, channels-last, the same arithmetic in both builds of the library -----------
+def convnd_f32(x: torch.Tensor, w: torch.Tensor, taps, stride, pad, *, bias: Optional[torch.Tensor] = None,
+               res: Optional[torch.Tensor] = None, rscale: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:
+    """x [n, t, h, w, cin], w [cout, ldw >= taps * cin] (tap-major, cin-minor) -> act(conv + bias + rscale * res) [n, to, ho, wo, cout];
+    see avsd_convnd_f32"""
+    for t, name in ((x, "x"), (w, "w"), (bias, "bias"), (res, "res"), (rscale, "rscale")):
+        if t is not None and (t.dtype != F32 or not t.is_cuda or not t.is_contiguous()):   # (a size-1 channel axis may carry any stride)
+            raise ValueError(f"convnd_f32: {name} must be a contiguous f32 device tensor")
+    if x.dim() != 5 or w.dim() != 2:
+        raise ValueError("convnd_f32: x must be [n, t, h, w, cin], w [cout, ldw]")
+    n, ti, hi, wi, cin = x.shape
+    cout, ldw = w.shape
+    (kt, kh, kw), (st, sh, sw), (pt, ph, pw) = taps, stride, pad
+    to, ho, wo = (ti + 2 * pt - kt) // st + 1, (hi + 2 * ph - kh) // sh + 1, (wi + 2 * pw - kw) // sw + 1
+    if min(to, ho, wo) < 1:
+        raise ValueError(f"convnd_f32: input {(ti, hi, wi)} is smaller than the window {tuple(taps)}")
+    if res is not None and tuple(res.shape) != (n, to, ho, wo, cout):
+        raise ValueError(f"convnd_f32: residual {tuple(res.shape)} does not match the output {(n, to, ho, wo, cout)}")
+    if any(v is not None and v.numel() != cout for v in (bias, rscale)):
+        raise ValueError("convnd_f32: bias / rscale must have cout entries")
+    out = torch.empty((n, to, ho, wo, cout), dtype=F32, device=x.device)
+    check(_lib.lib().avsd_convnd_f32(_p(x), _p(w), _p(bias), _p(res), _p(rscale), _p(out), n, ti, hi, wi, cin, to, ho, wo, cout,
+                                     kt, kh, kw, st, sh, sw, pt, ph, pw, ldw, int(relu), _stream()), "avsd_convnd_f32")
+    return out
+
+
+def maxpool_hw_f32(x: torch.Tensor) -> torch.Tensor:
+    """[n, t, h, w, c] -> [n, t, ho, wo, c]: (1, 3, 3) window, stride (1, 2, 2), padding (0, 1, 1)"""
+    _req(x, F32, "x")
+    if x.dim() != 5 or not x.is_contiguous():
+        raise ValueError("maxpool_hw_f32: x must be contiguous [n, t, h, w, c]")
+    n, t, hi, wi, c = x.shape
+    ho, wo = (hi - 1) // 2 + 1, (wi - 1) // 2 + 1
+    out = torch.empty((n, t, ho, wo, c), dtype=F32, device=x.device)
+    check(_lib.lib().avsd_maxpool_hw_f32(_p(x), _p(out), n * t, hi, wi, c, ho, wo, _stream()), "avsd_maxpool_hw_f32")
+    return out
+
+
+def mean_rows_f32(x: torch.Tensor) -> torch.Tensor:
+    """[n, ..., c] -> [n, c]: mean over all positions of a sample"""
+    _req(x, F32, "x")
+    if x.dim() < 2 or not x.is_contiguous():
+        raise ValueError("mean_rows_f32: x must be contiguous [n, ..., c]")
+    n, c = x.shape[0], x.shape[-1]
+    out = torch.empty((n, c), dtype=F32, device=x.device)
+    check(_lib.lib().avsd_mean_rows_f32(_p(x), _p(out), n, x.numel() // (n * c), c, _stream()), "avsd_mean_rows_f32")
+    return out
+
+
+def resize_aa_normalize_f32(frames: torch.Tensor, ytab, xtab, size: int, crop: int, mean, std) -> torch.Tensor:
+    """frames (n, 3, H, W) f32 -> [n, size, size, 3] resized with the host-built taps ytab / xtab = (start i32 [size], count i32 [size],
+    weight f32 [size, taps]) and normalised per channel; see avsd_resize_aa_normalize_f32"""
+    _req(frames, F32, "frames")
+    if frames.dim() != 4 or frames.shape[1] != 3 or not frames.is_contiguous():
+        raise ValueError("resize_aa_normalize_f32: frames must be contiguous (n, 3, H, W)")
+    n, _, hi, wi = frames.shape
+    for (s, cnt, wt), name in ((ytab, "ytab"), (xtab, "xtab")):
+        _req(wt, F32, name)
+        if s.dtype != torch.int32 or cnt.dtype != torch.int32 or s.numel() != size or cnt.numel() != size or wt.shape[0] != size \
+                or not (s.is_cuda and cnt.is_cuda and wt.is_contiguous()):
+            raise ValueError(f"resize_aa_normalize_f32: {name} must be (int32 [size], int32 [size], f32 [size, taps]) on the device")
+    tmp = torch.empty((n, 3, hi, size), dtype=F32, device=frames.device)
+    out = torch.empty((n, size, size, 3), dtype=F32, device=frames.device)
+    check(_lib.lib().avsd_resize_aa_normalize_f32(_p(frames), _p(tmp), _p(out), n, hi, wi, size, size, _p(ytab[0]), _p(ytab[1]), _p(ytab[2]),
+                                                  ytab[2].shape[1], _p(xtab[0]), _p(xtab[1]), _p(xtab[2]), xtab[2].shape[1], crop,
+                                                  *[float(v) for v in mean], *[float(v) for v in std], _stream()),
+          "avsd_resize_aa_normalize_f32")
+    return out

@@ -447,6 +447,36 @@ int avsd_vae_postprocess_u8_x2(const void* src, int ld, int64_t src_lo, void* ds
 int avsd_gemm_f32(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N, int K,
                   void* stream);
 
+/* ---- AVSync scorer (asva_amd/avsync.py; csrc/avsync.hip) ---------------------------------------------------------------------
+ * The reference's evaluation metric: the AVSync classifier (avsync/models/video.py R(2+1)D-18, audio.py 2-D conv net, head.py
+ * 3-layer FC) and RelSync on top of it (avgen/evaluations/avsync/compute_avsync.py:37-68).  Everything is f32 on the f32-input
+ * matrix cores in BOTH builds of the library, so a score does not depend on the storage mode of the clip it judges.
+ * Tensors are channels-last: video activations [n][t][h][w][c], audio activations the same with t = 1.
+ *
+ * Implicit-GEMM convolution with arbitrary small taps, strides and zero padding; no im2col buffer:
+ *   out[n, to, ho, wo, co] = act( sum_{dt, dh, dw, ci} x[n, to*st - pt + dt, ho*sh - ph + dh, wo*sw - pw + dw, ci]
+ *                                                      * w[co*ldw + ((dt*kh + dh)*kw + dw)*cin + ci]
+ *                                 + bias[co] + rscale[co] * res[n, to, ho, wo, co] ),   act = ReLU if `relu` else identity.
+ * bias, res, rscale may be NULL (rscale NULL = 1; rscale needs res).  Eval-mode BatchNorm folds into w / bias / rscale at pack
+ * time (video.py:38-43, audio.py:24-27).  With taps (1,1,1) and stride 1 this is A . W^T + b (head.py:14-22).  The output size
+ * must follow from input size, window, stride and padding.  Deterministic: every output element is one k-ordered chain. */
+int avsd_convnd_f32(const float* x, const float* w, const float* bias, const float* res, const float* rscale, float* out,
+                    int n, int ti, int hi, int wi, int cin, int to, int ho, int wo, int cout, int kt, int kh, int kw,
+                    int st, int sh, int sw, int pt, int ph, int pw, int ldw, int relu, void* stream);
+/* nn.MaxPool3d((1,3,3), stride (1,2,2), padding (0,1,1)) (video.py:62) on [n_img][hi][wi][c] -> [n_img][ho][wo][c]; padded
+ * positions do not take part.  c a multiple of 4. */
+int avsd_maxpool_hw_f32(const float* x, float* out, int n_img, int hi, int wi, int c, int ho, int wo, void* stream);
+/* x [n][rows][c] -> out [n][c] = mean over rows (video.py:80, audio.py:60); fixed summation order, no atomics. */
+int avsd_mean_rows_f32(const float* x, float* out, int n, int rows, int c, void* stream);
+/* Video preprocessing of compute_avsync.py:14-34: frames x (n_img, 3, hi, wi) f32 in [0, 1] -> out [n_img][ho][wo][3] =
+ * (antialiased bicubic resize - mean[c]) / std[c]; `crop` is the centre-crop size and must equal ho and wo (a no-op, as in the
+ * reference after its exact 224 x 224 resize).  The taps come from the host (asva_amd/avsync.py resize_tables): output row oy reads
+ * input rows y_start[oy] .. + y_count[oy] with weights y_weight[oy*y_taps + j]; columns likewise.  tmp: n_img*3*hi*wo floats. */
+int avsd_resize_aa_normalize_f32(const float* x, float* tmp, float* out, int n_img, int hi, int wi, int ho, int wo,
+                                 const int* y_start, const int* y_count, const float* y_weight, int y_taps,
+                                 const int* x_start, const int* x_count, const float* x_weight, int x_taps, int crop,
+                                 float mean0, float mean1, float mean2, float std0, float std1, float std2, void* stream);
+
 /* ---- launch plans (a host without Python runs the path) ----------------------------------------------------
  * A plan is the sequence of calls to the entry points above that one operation of the reference issues — the UNet forward
  * of a denoising step (audio_cond_unet_3d_condition.py:598-798), the per-clip conditioning projections, the VAE decode
