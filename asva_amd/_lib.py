@@ -137,6 +137,12 @@ SIGNATURES = {
     "avsd_mean_rows_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "avsd_resize_aa_normalize_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                              c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_float] * 6 + [c_void_p]),
+    # CLIP text encoder (csrc/clip_text.hip): f32 in both builds
+    "avsd_embed_tokens_f32": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
+    "avsd_layernorm_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p]),
+    "avsd_attention_causal_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                          c_void_p]),
+    "avsd_quick_gelu_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     # launch plans (asva_amd/plan.py records them; any host replays them)
     "avsd_plan_bundle_load": (c_int, [C.c_char_p, C.POINTER(c_void_p)]),
     "avsd_plan_bundle_free": (None, [c_void_p]),

@@ -1366,3 +1366,65 @@ def resize_aa_normalize_f32(frames: torch.Tensor, ytab, xtab, size: int, crop: i
                                                   *[float(v) for v in mean], *[float(v) for v in std], _stream()),
           "avsd_resize_aa_normalize_f32")
     return out
+
+
+# ---- CLIP text encoder (csrc/clip_text.hip): f32 tensors, the same arithmetic in both builds of the library --------------------
+def embed_tokens_f32(ids: torch.Tensor, tok: torch.Tensor, pos: torch.Tensor, b: int, seq: int) -> torch.Tensor:
+    """ids int32 [b * seq] (already checked against the table size on the host), tok [V, C], pos [>= seq, C] -> tok[ids] + pos, [b * seq, C]"""
+    _req(tok, F32, "tok")
+    _req(pos, F32, "pos")
+    if ids.dtype != torch.int32 or not ids.is_cuda or not ids.is_contiguous() or ids.numel() != b * seq:
+        raise ValueError("embed_tokens_f32: ids must be a contiguous int32 device tensor of b * seq entries")
+    if tok.dim() != 2 or pos.dim() != 2 or not tok.is_contiguous() or not pos.is_contiguous() or pos.shape[1] != tok.shape[1] or pos.shape[0] < seq:
+        raise ValueError("embed_tokens_f32: tok must be contiguous [V, C], pos contiguous [>= seq, C]")
+    v, c = tok.shape
+    out = torch.empty((b * seq, c), dtype=F32, device=tok.device)
+    check(_lib.lib().avsd_embed_tokens_f32(_p(ids), _p(tok), _p(pos), _p(out), b, seq, c, v, _stream()), "avsd_embed_tokens_f32")
+    return out
+
+
+def layernorm_f32(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [M, C] f32 (rows may be a column slice of a wider buffer) -> LayerNorm over C, [M, C]; `out` may be x"""
+    _req(x, F32, "x")
+    _req(gamma, F32, "gamma")
+    _req(beta, F32, "beta")
+    if x.dim() != 2 or gamma.numel() != x.shape[1] or beta.numel() != x.shape[1] or not gamma.is_contiguous() or not beta.is_contiguous():
+        raise ValueError("layernorm_f32: x must be [M, C], gamma and beta contiguous [C]")
+    m, c = x.shape
+    if out is None:
+        out = torch.empty((m, c), dtype=F32, device=x.device)
+    else:
+        _req(out, F32, "out")
+        if tuple(out.shape) != (m, c):
+            raise ValueError("layernorm_f32: out must have the shape of x")
+    ldx, ldy = (x.stride(0) if m > 1 else c), (out.stride(0) if m > 1 else c)
+    check(_lib.lib().avsd_layernorm_f32(_p(x), ldx, _p(out), ldy, m, c, _p(gamma), _p(beta), float(eps), _stream()), "avsd_layernorm_f32")
+    return out
+
+
+def attention_causal_f32(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, b: int, seq: int, heads: int,
+                         scale: Optional[float] = None) -> torch.Tensor:
+    """q, k, v [b * seq, heads * d] f32 (usually column slices of one fused [b * seq, 3 C] buffer) -> causal self-attention within each of
+    the b sequences, [b * seq, heads * d]; see avsd_attention_causal_f32"""
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        _req(t, F32, name)
+        if t.dim() != 2 or tuple(t.shape) != tuple(q.shape) or t.shape[0] != b * seq or t.shape[1] % heads:
+            raise ValueError(f"attention_causal_f32: {name} must be [b * seq, heads * d]")
+    c = q.shape[1]
+    d = c // heads
+    ld = [t.stride(0) if b * seq > 1 else c for t in (q, k, v)]
+    out = torch.empty((b * seq, c), dtype=F32, device=q.device)
+    check(_lib.lib().avsd_attention_causal_f32(_p(q), ld[0], _p(k), ld[1], _p(v), ld[2], _p(out), c, b, seq, heads, d,
+                                               float(d ** -0.5 if scale is None else scale), _stream()), "avsd_attention_causal_f32")
+    return out
+
+
+def quick_gelu_f32(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x * sigmoid(1.702 x) elementwise on a contiguous f32 tensor; `out` may be x"""
+    _req(x, F32, "x")
+    out = torch.empty_like(x) if out is None else out
+    _req(out, F32, "out")
+    if not x.is_contiguous() or not out.is_contiguous() or out.numel() != x.numel():
+        raise ValueError("quick_gelu_f32: x and out must be contiguous and of one size")
+    check(_lib.lib().avsd_quick_gelu_f32(_p(x), _p(out), x.numel(), _stream()), "avsd_quick_gelu_f32")
+    return out

@@ -32,6 +32,9 @@ from .vae import AutoencoderKL
 from .audio_features import AudioMelspectrogramExtractor
 
 MELSPECTROGRAM_SHAPE = (128, 204)   # pipeline_audio_cond_animation.py:77
+# True: generate_videos_for_dataset builds the tokenizer and the text encoder of asva_amd.text_encoder (f32 on the device library) instead
+# of transformers' (fp32 torch).  They are also used when transformers cannot be imported.
+native_text_encoder = False
 
 
 class AudioCondAnimationPipeline:
@@ -361,7 +364,14 @@ def generate_videos_for_dataset(exp_root: str, checkpoint: int, dataset: str = "
                                 device: torch.device = torch.device("cuda"), dtype: torch.dtype = torch.float16):
     """Reference generate_videos_for_dataset (:471-551) with one addition: when launched with one process per GPU
     (torchrun) the video list is sharded by rank (clip i -> rank i mod world) — the reference loops sequentially."""
-    from transformers import CLIPTextModel, CLIPTokenizer
+    CLIPTextModel = CLIPTokenizer = None
+    if not native_text_encoder:
+        try:
+            from transformers import CLIPTextModel, CLIPTokenizer
+        except ImportError:
+            pass
+    if CLIPTextModel is None:
+        from .text_encoder import CLIPTextModel, CLIPTokenizer
 
     # one process per GPU (torchrun): every rank owns cuda:LOCAL_RANK.  The unchanged reference script passes
     # torch.device("cuda") = cuda:0, which would stack all ranks on one GPU.

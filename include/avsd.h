@@ -1,6 +1,7 @@
 /*
  * avsd.h — C ABI of libavsd_hip.so: the MI355X (gfx950) kernels behind the AVSyncD
- * denoising path (per-step AudioUNet3D forward, CFG + scheduler update, VAE decode).
+ * denoising path (per-step AudioUNet3D forward, CFG + scheduler update, VAE decode), the audio
+ * front end, the AVSync scorer and the CLIP text encoder (f32 in both builds).
  *
  * The reference (lzhangbj/ASVA) has no FFI layer: its hot path is PyTorch module calls.
  * Each entry point below names the reference call site (file:line under /root/reference)
@@ -476,6 +477,32 @@ int avsd_resize_aa_normalize_f32(const float* x, float* tmp, float* out, int n_i
                                  const int* y_start, const int* y_count, const float* y_weight, int y_taps,
                                  const int* x_start, const int* x_count, const float* x_weight, int x_taps, int crop,
                                  float mean0, float mean1, float mean2, float std0, float std1, float std2, void* stream);
+
+/* ---- CLIP text encoder (asva_amd/text_encoder.py; csrc/clip_text.hip) --------------------------------------------------------
+ * The text_encoder of Stable Diffusion 1.5 (CLIP ViT-L/14 text tower: token + position embedding, 12 pre-LN blocks with causal
+ * self-attention and a quick-GELU MLP, final LayerNorm), which the reference calls through transformers
+ * (avgen/pipelines/pipeline_audio_cond_animation.py:83-119).  Everything is f32 on the f32-input matrix cores in BOTH builds of
+ * the library: a conditioning tensor does not move with the storage mode of the clip it conditions.  The linear layers are
+ * avsd_convnd_f32 with taps (1,1,1) (q|k|v as one fused [3C][C] weight, out_proj + residual, fc1, fc2 + residual).
+ *
+ * out[b*L + l][:] = tok[ids[b*L + l]][:] + pos[l][:]; ids int32 [B*L], tok f32 [V][C], pos f32 [L][C], out f32 [B*L][C].  The host
+ * checks 0 <= id < V before upload (the entry point cannot see device data); the kernel clamps an id into the table. */
+int avsd_embed_tokens_f32(const int* ids, const float* tok, const float* pos, float* out, int B, int L, int C, int V, void* stream);
+/* Row LayerNorm in f32: y[m][c] = (x[m][c] - mean_m) * rsqrt(var_m + eps) * gamma[c] + beta[c], two-pass variance
+ * (mean first, kept as a rounded value plus its correction, then the mean of squared deviations).  ldx / ldy are row strides in elements; y may equal x. */
+int avsd_layernorm_f32(const float* x, int ldx, float* y, int ldy, int M, int C, const float* gamma, const float* beta, float eps,
+                       void* stream);
+/* Causal self-attention of B sequences of length L: O[b*L + i][h*d + :] = sum_{j <= i} softmax_j(scale * Q_i . K_j) V_j over the keys
+ * of the SAME sequence.  Row r of Q / K / V / O is at r * ld{q,k,v,o} (elements), head h in columns [h*d, (h+1)*d): Q, K and V are
+ * usually views into one fused [B*L][3C] buffer.  Both products on v_mfma_f32_32x32x2_f32, softmax in f32; key tiles wholly above
+ * the diagonal of a query tile are skipped.  One workgroup per (sequence, head): a row's result does not depend on the batch it
+ * sits in, and every output element is one fixed-order chain.  Built for d == 64 and 1 <= L <= 128.
+ * K and V must be FINITE: a key j > i inside the 32-key tile that holds the diagonal gets probability 0 exactly, but its V row still
+ * enters the matrix product as 0 * V_j, and its K row a product that is then masked; an inf or NaN there gives NaN in row i. */
+int avsd_attention_causal_f32(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, int B,
+                              int L, int heads, int d, float scale, void* stream);
+/* y[i] = x[i] * sigmoid(1.702 x[i]) (CLIP's quick-GELU), i < n; y may equal x. */
+int avsd_quick_gelu_f32(const float* x, float* y, int64_t n, void* stream);
 
 /* ---- launch plans (a host without Python runs the path) ----------------------------------------------------
  * A plan is the sequence of calls to the entry points above that one operation of the reference issues — the UNet forward
