@@ -135,11 +135,16 @@ ASM_SPLITK_CANDIDATES = ((63, 2), (63, 4), (63, 8), (61, 2), (62, 2), (62, 4), (
                          (67, 2), (67, 3), (67, 4), (67, 5), (67, 6))
 ASM_TILES = tuple(range(60, 68))
 # column-tile width of the LDS-direct tile ids (gemm.hip dispatch_tile / dispatch_tile_x2): a sub-pixel upsample convolution (ups = 2) needs
-# whole column tiles per output-pixel parity, cout % BN == 0
+# whole column tiles per output-pixel parity, cout % BN == 0.  These constants, the candidate tuples above and what the two rules return
+# are hand copies of the `switch` statements in csrc/gemm.hip: tests/test_tile_choice_cpu.py parses that file and pins them
 SUBPIX_TILES = (4, 6, 9, 11, 13, 17, 20, 24, 25, 30, 38)          # gemm.hip avsd_gemm_dispatch_subpix / _x2_subpix
 SUBPIX_X2_TILES = (7, 11, 13, 24, 25, 34, 35)
 TILE_BN = {4: 64, 6: 128, 7: 64, 9: 128, 11: 128, 12: 64, 13: 64, 14: 128, 17: 320, 19: 320, 20: 128, 24: 64, 25: 64, 30: 128, 31: 256, 34: 160,
            35: 64, 36: 192, 38: 160}
+# a pick the sub-pixel loader is not built for -> the built tile of the same block (the deeper ring / the loader-wave form), and the
+# tile that stands for each column width when the pick has to narrow (128 x BN, the rule's own 128 x 128 / 128 x 64 picks)
+_SUBPIX_RELATIVE = {14: 20, 12: 24, 19: 17, 7: 25}
+_SUBPIX_BY_BN = ({320: 17, 160: 38, 128: 11, 64: 24}, {160: 34, 128: 11, 64: 24})
 ASM_X2_CANDIDATES = ((63, 1), (64, 1), (65, 1), (66, 1))        # split precision: 128x128 ... 64x64
 ASM_X2_SPLITK_CANDIDATES = ((63, 2), (63, 4), (64, 2), (64, 4), (65, 2), (65, 4), (66, 2), (66, 4), (66, 8))
 _ASM_TILES = True          # (module attribute: tools set it to False to time the LDS-direct tiles alone)
@@ -157,6 +162,26 @@ _KROT_MAX_W = 16 << 20
 def set_krot(on: bool) -> None:
     global _KROT
     _KROT = bool(on)
+
+
+def _subpix_tile(tile: int, cout: int, x2: bool) -> int:
+    """the tile a sub-pixel upsample convolution (ups = 2) runs on when the table or the rule named `tile`: `tile` itself if this loader
+    builds it and its column tiles are whole per output-pixel parity (cout % BN == 0, gemm.hip launch2), else its built relative, else the
+    widest built column tile that divides cout and is no wider than the pick.  cout % 64 == 0 (gemm()'s gate), so the 64-wide tiles make
+    this total.  Every tile of the two sets is LDS-direct and splits K, so the caller's split_k stands whatever comes back."""
+    if cout <= 0 or cout % 64:
+        raise ValueError(f"gemm: ups = 2 needs cout % 64 == 0 (got {cout})")
+    built = SUBPIX_X2_TILES if x2 else SUBPIX_TILES
+
+    def ok(t):
+        return t in built and cout % TILE_BN[t] == 0
+
+    if ok(tile):
+        return tile
+    if ok(_SUBPIX_RELATIVE.get(tile, 0)):
+        return _SUBPIX_RELATIVE[tile]
+    bn0 = TILE_BN.get(tile, 128)          # (register-staged, resident and asm ids carry no width here: treated as the 128-wide default)
+    return next(t for bn, t in sorted(_SUBPIX_BY_BN[int(x2)].items(), reverse=True) if bn <= max(bn0, 64) and ok(t))
 
 
 # A-resident, N-streaming tile (csrc/nstream.hip): the wide short-K projections whose weights the caller also holds in fragment order.
@@ -791,8 +816,8 @@ def gemm(
         if picked is None and two_src_conv:
             picked = _heuristic_conv3r(cands, M, N)
         tile, split_k = picked if picked is not None else heur(M, N, K, geglu, splitk_ok)
-        if mode == CONV3 and d.ups == 2 and (tile not in (SUBPIX_X2_TILES if x2 else SUBPIX_TILES) or (N // 4) % TILE_BN[tile]):
-            tile = {14: 20, 12: 24}.get(tile, 11)      # (the rule named a tile this loader is not built for: its nearest built relative)
+        if mode == CONV3 and d.ups == 2:
+            tile = _subpix_tile(tile, N // 4, x2)      # (the rule may name a tile this loader is not built for, or one wider than a divisor of cout)
     _set(tile, split_k)
     ev = _TIMER.start() if _TIMER is not None else None
     check(_lib.lib().avsd_gemm_bf16(C.byref(d), _stream()), "avsd_gemm_bf16")
