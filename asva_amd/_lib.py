@@ -143,6 +143,13 @@ SIGNATURES = {
     "avsd_attention_causal_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
                                           c_void_p]),
     "avsd_quick_gelu_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    # ImageBind evaluation towers (csrc/imagebind_eval.hip): f32 in both builds
+    "avsd_attention_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                   c_void_p]),
+    "avsd_gelu_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "avsd_vit_tokens_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "avsd_cosine_rows_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "avsd_normalize_rows_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     # launch plans (asva_amd/plan.py records them; any host replays them)
     "avsd_plan_bundle_load": (c_int, [C.c_char_p, C.POINTER(c_void_p)]),
     "avsd_plan_bundle_free": (None, [c_void_p]),

@@ -479,20 +479,23 @@ _NETS: Dict[str, AVSyncClassifier] = {}
 def compute_sync_metrics_on_av(audio_waveform: torch.Tensor, audio_sr: int, video: torch.Tensor,
                                ref_audio_waveform: Optional[torch.Tensor] = None, ref_audio_sr: Optional[int] = None,
                                ref_video: Optional[torch.Tensor] = None, metric: str = "alignsync", device=torch.device("cuda"),
-                               dtype: torch.dtype = torch.float32, net: Optional[AVSyncClassifier] = None):
-    """compute_avsync.py:105-end for metric in ("relsync", "avsync_score"): waveform (c, samples) at 16 kHz, video (3, 12, h, w) in
-    [0, 1].  `net` defaults to load_avsync_model() (loaded once per process)."""
+                               dtype: torch.dtype = torch.float32, net: Optional[AVSyncClassifier] = None, clip_net=None):
+    """compute_avsync.py:105-end: waveform (c, samples) at 16 kHz, video (3, 12, h, w) in [0, 1].  `net` defaults to
+    load_avsync_model() (loaded once per process).  metric="alignsync" needs `ref_video` and `clip_net`, the ImageBind towers of
+    asva_amd.imagebind_eval.load_clip_model(path): their checkpoint is not fetched here."""
     from .audio_features import waveform_to_melspectrogram
 
     if metric not in ("alignsync", "relsync", "avsync_score"):
         raise ValueError(f"unknown metric {metric!r}")
-    if metric == "alignsync":
-        raise NotImplementedError("alignsync multiplies RelSync by an ImageBind image-audio similarity; the ImageBind vision trunk is "
-                                  "not part of this package")
+    if metric == "alignsync" and clip_net is None:
+        raise NotImplementedError("alignsync multiplies RelSync by an ImageBind image-audio similarity and no ImageBind checkpoint is "
+                                  "fetched here: pass clip_net=load_clip_model(path) (asva_amd.imagebind_eval)")
     if dtype != torch.float32:
         raise ValueError("the scorer computes in float32 only")
     if video.dim() != 4 or video.shape[1] != 12:
         raise ValueError("video should be (3, 12, h, w): 12 frames at 6 FPS")
+    if metric == "alignsync" and (ref_video is None or tuple(ref_video.shape) != tuple(video.shape)):
+        raise ValueError("To compute alignsync, ref_video is needed as reference, and in the same shape as video")
     if metric == "relsync" and (ref_audio_waveform is None) == (ref_video is None):
         raise ValueError("To compute relsync, either ref_audio_waveform or ref_video is needed as reference")
     ref_audio_sr = audio_sr if ref_audio_sr is None else ref_audio_sr
@@ -511,6 +514,10 @@ def compute_sync_metrics_on_av(audio_waveform: torch.Tensor, audio_sr: int, vide
     video = video.unsqueeze(0).to(device=device, dtype=dtype)
     if metric == "avsync_score":
         return compute_avsync_scores(audio, video, net)[0]
+    if metric == "alignsync":
+        from .imagebind_eval import compute_alignsync
+
+        return compute_alignsync(audio, video, ref_video.unsqueeze(0).to(device=device, dtype=dtype), net, clip_net.to(device))[0]
     if ref_audio_waveform is not None:
         return compute_relsync(audio, video, net, ref_audios=mel(ref_audio_waveform))[0]
     return compute_relsync(audio, video, net, ref_videos=ref_video.unsqueeze(0).to(device=device, dtype=dtype))[0]

@@ -78,6 +78,9 @@ const Entry kEntries[] = {
     // CLIP text encoder (csrc/clip_text.hip)
     AVSD_PLAN_ENTRY(avsd_embed_tokens_f32), AVSD_PLAN_ENTRY(avsd_layernorm_f32),         AVSD_PLAN_ENTRY(avsd_attention_causal_f32),
     AVSD_PLAN_ENTRY(avsd_quick_gelu_f32),
+    // ImageBind evaluation towers (csrc/imagebind_eval.hip)
+    AVSD_PLAN_ENTRY(avsd_attention_f32),    AVSD_PLAN_ENTRY(avsd_gelu_f32),              AVSD_PLAN_ENTRY(avsd_vit_tokens_f32),
+    AVSD_PLAN_ENTRY(avsd_cosine_rows_f32),   AVSD_PLAN_ENTRY(avsd_normalize_rows_f32),
 };
 
 struct Reloc {

@@ -1453,3 +1453,69 @@ def quick_gelu_f32(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch
         raise ValueError("quick_gelu_f32: x and out must be contiguous and of one size")
     check(_lib.lib().avsd_quick_gelu_f32(_p(x), _p(out), x.numel(), _stream()), "avsd_quick_gelu_f32")
     return out
+
+
+# ---- ImageBind evaluation towers (csrc/imagebind_eval.hip): f32 tensors, the same arithmetic in both builds of the library --------
+def attention_f32(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, b: int, seq: int, heads: int, scale: Optional[float] = None) -> torch.Tensor:
+    """q, k, v [b * seq, heads * d] f32 (usually column slices of one fused [b * seq, 3 C] buffer) -> bidirectional self-attention within
+    each of the b sequences, [b * seq, heads * d]; d is 64 or 80; see avsd_attention_f32"""
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        _req(t, F32, name)
+        if t.dim() != 2 or tuple(t.shape) != tuple(q.shape) or t.shape[0] != b * seq or t.shape[1] % heads:
+            raise ValueError(f"attention_f32: {name} must be [b * seq, heads * d]")
+    c = q.shape[1]
+    d = c // heads
+    ld = [t.stride(0) if b * seq > 1 else c for t in (q, k, v)]
+    out = torch.empty((b * seq, c), dtype=F32, device=q.device)
+    check(_lib.lib().avsd_attention_f32(_p(q), ld[0], _p(k), ld[1], _p(v), ld[2], _p(out), c, b, seq, heads, d,
+                                        float(d ** -0.5 if scale is None else scale), _stream()), "avsd_attention_f32")
+    return out
+
+
+def gelu_f32(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """0.5 x (1 + erf(x / sqrt 2)) elementwise on a contiguous f32 tensor; `out` may be x"""
+    _req(x, F32, "x")
+    out = torch.empty_like(x) if out is None else out
+    _req(out, F32, "out")
+    if not x.is_contiguous() or not out.is_contiguous() or out.numel() != x.numel():
+        raise ValueError("gelu_f32: x and out must be contiguous and of one size")
+    check(_lib.lib().avsd_gelu_f32(_p(x), _p(out), x.numel(), _stream()), "avsd_gelu_f32")
+    return out
+
+
+def vit_tokens_f32(patches: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, b: int, tail_rows: int = 0) -> torch.Tensor:
+    """f32 patch embeddings [b * np, C] + cls [C] + pos [1 + np, C] -> f32 [b * (1 + np + tail_rows), C] with zero tail rows"""
+    _req(patches, F32, "patches")
+    _req(cls, F32, "cls")
+    _req(pos, F32, "pos")
+    if patches.dim() != 2 or b < 1 or patches.shape[0] % b:
+        raise ValueError("vit_tokens_f32: patches must be [b * np, C]")
+    n_p, c = patches.shape[0] // b, patches.shape[1]
+    if not (patches.is_contiguous() and cls.is_contiguous() and pos.is_contiguous()) or tuple(pos.shape) != (1 + n_p, c) or cls.numel() != c:
+        raise ValueError("vit_tokens_f32: patches contiguous [b * np, C], cls [C], pos contiguous [1 + np, C]")
+    out = torch.empty((b * (1 + n_p + tail_rows), c), dtype=F32, device=patches.device)
+    check(_lib.lib().avsd_vit_tokens_f32(_p(patches), _p(cls), _p(pos), _p(out), b, n_p, c, tail_rows, _stream()), "avsd_vit_tokens_f32")
+    return out
+
+
+def cosine_rows_f32(x: torch.Tensor, y: torch.Tensor, rep: int = 1) -> torch.Tensor:
+    """x [m, C], y [m / rep, C] f32 -> [m]: the cosine of row i of x and row i // rep of y, norms clamped at 1e-12 as F.normalize"""
+    _req(x, F32, "x")
+    _req(y, F32, "y")
+    if x.dim() != 2 or y.dim() != 2 or not x.is_contiguous() or not y.is_contiguous() or x.shape[1] != y.shape[1] or rep < 1 \
+            or y.shape[0] * rep != x.shape[0]:
+        raise ValueError(f"cosine_rows_f32: x contiguous [m, C] and y contiguous [m / rep, C], got {tuple(x.shape)}, {tuple(y.shape)}, rep {rep}")
+    out = torch.empty((x.shape[0],), dtype=F32, device=x.device)
+    check(_lib.lib().avsd_cosine_rows_f32(_p(x), _p(y), _p(out), x.shape[0], x.shape[1], rep, _stream()), "avsd_cosine_rows_f32")
+    return out
+
+
+def normalize_rows_f32(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [m, C] contiguous f32 -> rows divided by max(their L2 norm, 1e-12), as F.normalize; `out` may be x"""
+    _req(x, F32, "x")
+    out = torch.empty_like(x) if out is None else out
+    _req(out, F32, "out")
+    if x.dim() != 2 or not x.is_contiguous() or not out.is_contiguous() or tuple(out.shape) != tuple(x.shape):
+        raise ValueError("normalize_rows_f32: x and out must be contiguous [m, C]")
+    check(_lib.lib().avsd_normalize_rows_f32(_p(x), _p(out), x.shape[0], x.shape[1], _stream()), "avsd_normalize_rows_f32")
+    return out

@@ -1,7 +1,7 @@
 /*
  * avsd.h — C ABI of libavsd_hip.so: the MI355X (gfx950) kernels behind the AVSyncD
  * denoising path (per-step AudioUNet3D forward, CFG + scheduler update, VAE decode), the audio
- * front end, the AVSync scorer and the CLIP text encoder (f32 in both builds).
+ * front end, the AVSync scorer, the CLIP text encoder and the ImageBind evaluation towers (f32 in both builds).
  *
  * The reference (lzhangbj/ASVA) has no FFI layer: its hot path is PyTorch module calls.
  * Each entry point below names the reference call site (file:line under /root/reference)
@@ -503,6 +503,38 @@ int avsd_attention_causal_f32(const float* Q, int ldq, const float* K, int ldk, 
                               int L, int heads, int d, float scale, void* stream);
 /* y[i] = x[i] * sigmoid(1.702 x[i]) (CLIP's quick-GELU), i < n; y may equal x. */
 int avsd_quick_gelu_f32(const float* x, float* y, int64_t n, void* stream);
+
+/* ---- ImageBind evaluation towers: CLIPSim and AlignSync (asva_amd/imagebind_eval.py; csrc/imagebind_eval.hip) -------------------
+ * The reference scores a clip with ImageBind-Huge embeddings (avgen/evaluations/models/clip.py:23-80): a ViT-H/14 vision tower
+ * (257 tokens, 32 blocks, 16 heads of 80), an OpenCLIP-H text tower (77 tokens, causal: avsd_attention_causal_f32) and the audio
+ * trunk (229 tokens + the bias_kv pair, 12 heads of 64).  f32 on the f32-input matrix cores in BOTH builds of the library, bit for
+ * bit the same: a metric does not move with the storage mode of the clip it judges.  Linear layers and patch embeddings are
+ * avsd_convnd_f32, LayerNorm is avsd_layernorm_f32.
+ *
+ * Bidirectional self-attention of B sequences of length L: O[b*L + i][h*d + :] = sum_j softmax_j(scale * Q_i . K_j) V_j over ALL keys
+ * of the same sequence.  Row r of Q / K / V / O is at r * ld{q,k,v,o} (elements), head h in columns [h*d, (h+1)*d): Q, K and V are
+ * usually views into one fused [B*L][3C] buffer.  Grid (128-query block, head, sequence); K and V stream through LDS in 64-key tiles
+ * with a running maximum and denominator per query, so L is not bounded by LDS.  Both products on v_mfma_f32_32x32x2_f32, softmax in
+ * f32 with libm's expf.  Keys past L get weight exactly 0, query rows past L are never stored, and for d = 80 the pad to the 32-channel
+ * MFMA tile is zeros held in LDS: no column outside the head is read.  Every output element is one chain in a fixed key order: the
+ * result of a row does not depend on B, on the query block it lands in, or on the build.  Built for d == 64 and d == 80, L >= 1.
+ * K, V and O must be 16-byte aligned with row strides a multiple of 4. */
+int avsd_attention_f32(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, int B, int L,
+                       int heads, int d, float scale, void* stream);
+/* y[i] = 0.5 x[i] (1 + erf(x[i] / sqrt 2)) (erf-GELU, torch's F.gelu default), i < n; y may equal x.  Finite for any finite x. */
+int avsd_gelu_f32(const float* x, float* y, int64_t n, void* stream);
+/* avsd_vit_tokens in f32: patches f32 [B*n_patches][C], cls f32 [C], pos f32 [1 + n_patches][C] ->
+ * out f32 [B*(1 + n_patches + tail_rows)][C]: row 0 = cls + pos[0], rows 1.. = patches + pos[1..], tail rows = 0 (the audio trunk keeps
+ * one spare row per clip for its bias_kv pair). */
+int avsd_vit_tokens_f32(const float* patches, const float* cls, const float* pos, float* out, int B, int n_patches, int C, int tail_rows,
+                        void* stream);
+/* out[i] = <x_i, y_{i / rep}> / (max(|x_i|, 1e-12) * max(|y_{i / rep}|, 1e-12)), i < m: the cosine of row i of x f32 [m][C] and row
+ * i / rep of y f32 [m / rep][C] with the norms of F.normalize (a zero row gives 0).  rep must divide m: one audio or text embedding
+ * per clip is broadcast over that clip's rep frames.  One wave per row, fixed summation order. */
+int avsd_cosine_rows_f32(const float* x, const float* y, float* out, int m, int C, int rep, void* stream);
+/* y[i][:] = x[i][:] / max(|x_i|, 1e-12) for the m rows of x f32 [m][C] (F.normalize); y may equal x.  One wave per row, the summation
+ * order of avsd_cosine_rows_f32: a row's result does not depend on m. */
+int avsd_normalize_rows_f32(const float* x, float* y, int m, int C, void* stream);
 
 /* ---- launch plans (a host without Python runs the path) ----------------------------------------------------
  * A plan is the sequence of calls to the entry points above that one operation of the reference issues — the UNet forward
