@@ -3,6 +3,8 @@
 // preprocessing of avgen/evaluations/avsync/compute_avsync.py:14-34.  A metric must not move with the storage mode of what it
 // measures, so NOTHING here uses the 16-bit type of the build: tensors are f32, products run on the f32-input matrix cores
 // (v_mfma_f32_32x32x2_f32, as csrc/gemm_f32.hip), and the bf16 and fp16 libraries compile this file to the same arithmetic.
+// Also here, because they share the convolution body: the two kernels Inception-v3 adds for FID (asva_amd/fid.py) — the convolution
+// on channel slices of wider buffers (avsd_convnd_ld_f32) and the 3 x 3 pools (avsd_pool3_hw_f32).
 //
 // Layout: channels-last f32, video activations [n][t][h][w][c], audio activations the same with t = 1.
 #include "avsd_common.h"
@@ -22,11 +24,20 @@ struct ConvGeom {
   int kt, kh, kw, st, sh, sw, pt, ph, pw;
   int ldw, relu, M, K;
 };
+// avsd_convnd_ld_f32: the strides between pixels of x (ldx >= cin) and of out / res (ldy >= cout), in elements; x and out may
+// be channel slices of wider channels-last buffers.  The dense kernel does not carry them: its code stays what it was.
+struct ConvLd {
+  int ldx, ldy;
+};
 
-template <int FM, int FN, bool VEC>
-__global__ __launch_bounds__(256) void convnd_f32_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                         const float* __restrict__ bias, const float* __restrict__ res,
-                                                         const float* __restrict__ rscale, float* __restrict__ out, ConvGeom g) {
+// LD = false: pixels are cin / cout elements apart (avsd_convnd_f32); LD = true: ld.ldx / ld.ldy apart.  Only addresses differ:
+// the chain of every output element is the same in both.
+template <int FM, int FN, bool VEC, bool LD>
+__device__ __forceinline__ void convnd_f32_body(const float* __restrict__ x, const float* __restrict__ w,
+                                                const float* __restrict__ bias, const float* __restrict__ res,
+                                                const float* __restrict__ rscale, float* __restrict__ out, const ConvGeom& g,
+                                                const ConvLd& ld) {
+  const int ldx = LD ? ld.ldx : g.cin, ldy = LD ? ld.ldy : g.cout;
   constexpr int BM = 64 * FM, BN = 64 * FN;
   constexpr int NA = VEC ? BM / 32 : BM / 8;      // A elements (float4 / float) each thread fetches per K tile
   constexpr int NW = VEC ? BN / 32 : BN / 8;
@@ -76,7 +87,7 @@ __global__ __launch_bounds__(256) void convnd_f32_kernel(const float* __restrict
         const int4 rv = sRow[lr + 32 * i];
         const int t = rv.y + dt, h = rv.z + dh, ww = rv.w + dw;
         const bool ok = (unsigned)t < (unsigned)g.ti && (unsigned)h < (unsigned)g.hi && (unsigned)ww < (unsigned)g.wi;
-        ra[i] = ok ? *reinterpret_cast<const float4*>(x + ((((int64_t)rv.x * g.ti + t) * g.hi + h) * g.wi + ww) * g.cin + c)
+        ra[i] = ok ? *reinterpret_cast<const float4*>(x + ((((int64_t)rv.x * g.ti + t) * g.hi + h) * g.wi + ww) * ldx + c)
                    : make_float4(0.f, 0.f, 0.f, 0.f);
       }
 #pragma unroll
@@ -94,7 +105,7 @@ __global__ __launch_bounds__(256) void convnd_f32_kernel(const float* __restrict
         const int4 rv = sRow[lr + 8 * i];
         const int t = rv.y + dt, h = rv.z + dh, ww = rv.w + dw;
         const bool ok = kok && (unsigned)t < (unsigned)g.ti && (unsigned)h < (unsigned)g.hi && (unsigned)ww < (unsigned)g.wi;
-        fa[i] = ok ? x[((((int64_t)rv.x * g.ti + t) * g.hi + h) * g.wi + ww) * g.cin + c] : 0.f;
+        fa[i] = ok ? x[((((int64_t)rv.x * g.ti + t) * g.hi + h) * g.wi + ww) * ldx + c] : 0.f;
       }
 #pragma unroll
       for (int i = 0; i < NW; ++i) {
@@ -159,18 +170,79 @@ __global__ __launch_bounds__(256) void convnd_f32_kernel(const float* __restrict
         const int m = m0 + wm * 32 * FM + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
         if (m >= M) continue;
         float v = acc[a][b][r] + bv;
-        if (res) v += rs * res[(int64_t)m * g.cout + nn];
+        if (res) v += rs * res[(int64_t)m * ldy + nn];
         if (g.relu) v = fmaxf(v, 0.f);
-        out[(int64_t)m * g.cout + nn] = v;
+        out[(int64_t)m * ldy + nn] = v;
       }
     }
 }
 
+template <int FM, int FN, bool VEC>
+__global__ __launch_bounds__(256) void convnd_f32_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                         const float* __restrict__ bias, const float* __restrict__ res,
+                                                         const float* __restrict__ rscale, float* __restrict__ out, ConvGeom g) {
+  convnd_f32_body<FM, FN, VEC, false>(x, w, bias, res, rscale, out, g, ConvLd{0, 0});
+}
+template <int FM, int FN, bool VEC>
+__global__ __launch_bounds__(256) void convnd_ld_f32_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                            const float* __restrict__ bias, const float* __restrict__ res,
+                                                            const float* __restrict__ rscale, float* __restrict__ out, ConvGeom g,
+                                                            ConvLd ld) {
+  convnd_f32_body<FM, FN, VEC, true>(x, w, bias, res, rscale, out, g, ld);
+}
+
 template <int FM, int FN>
 void launch_conv(bool vec, dim3 grid, hipStream_t s, const float* x, const float* w, const float* bias, const float* res,
-                 const float* rscale, float* out, const ConvGeom& g) {
-  if (vec) hipLaunchKernelGGL((convnd_f32_kernel<FM, FN, true>), grid, dim3(256), 0, s, x, w, bias, res, rscale, out, g);
-  else hipLaunchKernelGGL((convnd_f32_kernel<FM, FN, false>), grid, dim3(256), 0, s, x, w, bias, res, rscale, out, g);
+                 const float* rscale, float* out, const ConvGeom& g, const ConvLd* ld) {
+  if (ld) {
+    if (vec) hipLaunchKernelGGL((convnd_ld_f32_kernel<FM, FN, true>), grid, dim3(256), 0, s, x, w, bias, res, rscale, out, g, *ld);
+    else hipLaunchKernelGGL((convnd_ld_f32_kernel<FM, FN, false>), grid, dim3(256), 0, s, x, w, bias, res, rscale, out, g, *ld);
+  } else {
+    if (vec) hipLaunchKernelGGL((convnd_f32_kernel<FM, FN, true>), grid, dim3(256), 0, s, x, w, bias, res, rscale, out, g);
+    else hipLaunchKernelGGL((convnd_f32_kernel<FM, FN, false>), grid, dim3(256), 0, s, x, w, bias, res, rscale, out, g);
+  }
+}
+
+// checks and tile choice shared by avsd_convnd_f32 (ld == nullptr) and avsd_convnd_ld_f32
+int convnd_dispatch(const char* who, const float* x, const float* w, const float* bias, const float* res, const float* rscale, float* out,
+                    int n, int ti, int hi, int wi, int cin, int to, int ho, int wo, int cout, int kt, int kh, int kw, int st, int sh,
+                    int sw, int pt, int ph, int pw, int ldw, int relu, const ConvLd* ld, void* stream) {
+  AVSD_REQUIRE(x && w && out, "%s: null pointer", who);
+  AVSD_REQUIRE(n > 0 && ti > 0 && hi > 0 && wi > 0 && cin > 0 && cout > 0, "%s: sizes must be positive", who);
+  AVSD_REQUIRE(kt > 0 && kh > 0 && kw > 0 && kt <= 16 && kh <= 16 && kw <= 16 && st > 0 && sh > 0 && sw > 0,
+               "%s: taps must be 1 .. 16 and strides positive", who);
+  AVSD_REQUIRE(pt >= 0 && ph >= 0 && pw >= 0 && pt < kt && ph < kh && pw < kw, "%s: padding must be smaller than the window", who);
+  AVSD_REQUIRE(ti + 2 * pt >= kt && hi + 2 * ph >= kh && wi + 2 * pw >= kw, "%s: the window does not fit the padded input", who);
+  AVSD_REQUIRE(to == (ti + 2 * pt - kt) / st + 1 && ho == (hi + 2 * ph - kh) / sh + 1 && wo == (wi + 2 * pw - kw) / sw + 1,
+               "%s: output size (%d, %d, %d) does not follow from input (%d, %d, %d), window, stride and padding", who, to, ho, wo,
+               ti, hi, wi);
+  const int64_t K64 = (int64_t)kt * kh * kw * cin, M64 = (int64_t)n * to * ho * wo;
+  AVSD_REQUIRE(ldw >= K64, "%s: ldw %d is smaller than K = taps * cin = %lld", who, ldw, (long long)K64);
+  AVSD_REQUIRE(M64 < (1ll << 31) && K64 < (1ll << 24) && (int64_t)n * ti * hi * wi < (1ll << 31), "%s: tensor too large", who);
+  AVSD_REQUIRE(!rscale || res, "%s: rscale without a residual", who);
+  if (ld) {
+    AVSD_REQUIRE(ld->ldx >= cin, "%s: ldx %d is smaller than cin %d", who, ld->ldx, cin);
+    AVSD_REQUIRE(ld->ldy >= cout, "%s: ldy %d is smaller than cout %d", who, ld->ldy, cout);
+  }
+  const bool vec = cin % CK == 0 && ldw % 4 == 0 && ((uintptr_t)x | (uintptr_t)w) % 16 == 0 && (!ld || ld->ldx % 4 == 0);
+  ConvGeom g{n, ti, hi, wi, cin, to, ho, wo, cout, kt, kh, kw, st, sh, sw, pt, ph, pw, ldw, relu ? 1 : 0, (int)M64, (int)K64};
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  // tile by shape alone (the result does not depend on it): 64 output channels get a 64-wide tile; a layer too small to give
+  // every CU a 128-row tile runs on 64 x 64 tiles
+  const int fn = cout <= 64 ? 1 : 2;
+  const int64_t big = ((M64 + 127) / 128) * ((cout + 64 * fn - 1) / (64 * fn));
+  if (big < 256) {
+    dim3 grid((unsigned)((cout + 63) / 64), (unsigned)((M64 + 63) / 64));
+    launch_conv<1, 1>(vec, grid, s, x, w, bias, res, rscale, out, g, ld);
+  } else if (fn == 1) {
+    dim3 grid((unsigned)((cout + 63) / 64), (unsigned)((M64 + 127) / 128));
+    launch_conv<2, 1>(vec, grid, s, x, w, bias, res, rscale, out, g, ld);
+  } else {
+    dim3 grid((unsigned)((cout + 127) / 128), (unsigned)((M64 + 127) / 128));
+    launch_conv<2, 2>(vec, grid, s, x, w, bias, res, rscale, out, g, ld);
+  }
+  AVSD_CHECK_LAUNCH(ld ? "convnd_ld_f32 launch" : "convnd_f32 launch");
+  return AVSD_OK;
 }
 
 // ---- avsd_maxpool_hw_f32: (1, 3, 3) window, stride (1, 2, 2), padding (0, 1, 1); one thread per output pixel and 4 channels ---------
@@ -198,6 +270,47 @@ __global__ __launch_bounds__(256) void maxpool_hw_f32_kernel(const float* __rest
     }
   }
   reinterpret_cast<float4*>(out)[idx] = m;
+}
+
+// ---- avsd_pool3_hw_f32: 3 x 3 window of Inception-v3 (asva_amd/fid.py), stride S and padding P in {(2, 0), (1, 1)}; one thread per
+// output pixel and 4 channels.  Pixels of x are ldx elements apart and pixels of out ldy: either may be a channel slice of a wider
+// buffer.  AVG: the taps inside the image are summed in (dy, dx) order and divided by their number (count_include_pad=False);
+// otherwise the maximum over them.  Padded positions never take part. -----------------------------------------------------------------
+template <bool AVG>
+__global__ __launch_bounds__(256) void pool3_hw_f32_kernel(const float* __restrict__ x, float* __restrict__ out, int hi, int wi, int c4,
+                                                           int ldx, int ldy, int ho, int wo, int S, int P, int64_t total) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int c = (int)(idx % c4);
+  int64_t q = idx / c4;
+  const int ox = (int)(q % wo); q /= wo;
+  const int oy = (int)(q % ho);
+  const int64_t img = q / ho;
+  const float* src = x + img * hi * wi * ldx + 4 * c;
+  float4 m = AVG ? make_float4(0.f, 0.f, 0.f, 0.f) : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+  int cnt = 0;
+#pragma unroll
+  for (int dy = 0; dy < 3; ++dy) {
+    const int y = S * oy - P + dy;
+    if ((unsigned)y >= (unsigned)hi) continue;
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx) {
+      const int xx = S * ox - P + dx;
+      if ((unsigned)xx >= (unsigned)wi) continue;
+      const float4 v = *reinterpret_cast<const float4*>(src + ((int64_t)y * wi + xx) * ldx);
+      if constexpr (AVG) {
+        m.x += v.x; m.y += v.y; m.z += v.z; m.w += v.w;
+      } else {
+        m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+      }
+      ++cnt;
+    }
+  }
+  if constexpr (AVG) {
+    const float d = (float)cnt;      // >= 1: the entry point admits only windows that meet the image
+    m.x /= d; m.y /= d; m.z /= d; m.w /= d;
+  }
+  *reinterpret_cast<float4*>(out + ((img * ho + oy) * wo + ox) * ldy + 4 * c) = m;
 }
 
 // ---- avsd_mean_rows_f32: x [n][rows][c] -> out [n][c].  Thread (channel, quarter q): rows q, q + 4, ... in order, accumulated in
@@ -259,38 +372,16 @@ __global__ __launch_bounds__(256) void resize_v_norm_f32_kernel(const float* __r
 extern "C" int avsd_convnd_f32(const float* x, const float* w, const float* bias, const float* res, const float* rscale, float* out,
                                int n, int ti, int hi, int wi, int cin, int to, int ho, int wo, int cout, int kt, int kh, int kw,
                                int st, int sh, int sw, int pt, int ph, int pw, int ldw, int relu, void* stream) {
-  AVSD_REQUIRE(x && w && out, "convnd_f32: null pointer");
-  AVSD_REQUIRE(n > 0 && ti > 0 && hi > 0 && wi > 0 && cin > 0 && cout > 0, "convnd_f32: sizes must be positive");
-  AVSD_REQUIRE(kt > 0 && kh > 0 && kw > 0 && kt <= 16 && kh <= 16 && kw <= 16 && st > 0 && sh > 0 && sw > 0,
-               "convnd_f32: taps must be 1 .. 16 and strides positive");
-  AVSD_REQUIRE(pt >= 0 && ph >= 0 && pw >= 0 && pt < kt && ph < kh && pw < kw, "convnd_f32: padding must be smaller than the window");
-  AVSD_REQUIRE(ti + 2 * pt >= kt && hi + 2 * ph >= kh && wi + 2 * pw >= kw, "convnd_f32: the window does not fit the padded input");
-  AVSD_REQUIRE(to == (ti + 2 * pt - kt) / st + 1 && ho == (hi + 2 * ph - kh) / sh + 1 && wo == (wi + 2 * pw - kw) / sw + 1,
-               "convnd_f32: output size (%d, %d, %d) does not follow from input (%d, %d, %d), window, stride and padding", to, ho, wo,
-               ti, hi, wi);
-  const int64_t K64 = (int64_t)kt * kh * kw * cin, M64 = (int64_t)n * to * ho * wo;
-  AVSD_REQUIRE(ldw >= K64, "convnd_f32: ldw %d is smaller than K = taps * cin = %lld", ldw, (long long)K64);
-  AVSD_REQUIRE(M64 < (1ll << 31) && K64 < (1ll << 24) && (int64_t)n * ti * hi * wi < (1ll << 31), "convnd_f32: tensor too large");
-  AVSD_REQUIRE(!rscale || res, "convnd_f32: rscale without a residual");
-  const bool vec = cin % CK == 0 && ldw % 4 == 0 && ((uintptr_t)x | (uintptr_t)w) % 16 == 0;
-  ConvGeom g{n, ti, hi, wi, cin, to, ho, wo, cout, kt, kh, kw, st, sh, sw, pt, ph, pw, ldw, relu ? 1 : 0, (int)M64, (int)K64};
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  // tile by shape alone (the result does not depend on it): 64 output channels get a 64-wide tile; a layer too small to give
-  // every CU a 128-row tile runs on 64 x 64 tiles
-  const int fn = cout <= 64 ? 1 : 2;
-  const int64_t big = ((M64 + 127) / 128) * ((cout + 64 * fn - 1) / (64 * fn));
-  if (big < 256) {
-    dim3 grid((unsigned)((cout + 63) / 64), (unsigned)((M64 + 63) / 64));
-    launch_conv<1, 1>(vec, grid, s, x, w, bias, res, rscale, out, g);
-  } else if (fn == 1) {
-    dim3 grid((unsigned)((cout + 63) / 64), (unsigned)((M64 + 127) / 128));
-    launch_conv<2, 1>(vec, grid, s, x, w, bias, res, rscale, out, g);
-  } else {
-    dim3 grid((unsigned)((cout + 127) / 128), (unsigned)((M64 + 127) / 128));
-    launch_conv<2, 2>(vec, grid, s, x, w, bias, res, rscale, out, g);
-  }
-  AVSD_CHECK_LAUNCH("convnd_f32 launch");
-  return AVSD_OK;
+  return convnd_dispatch("convnd_f32", x, w, bias, res, rscale, out, n, ti, hi, wi, cin, to, ho, wo, cout, kt, kh, kw, st, sh, sw, pt, ph,
+                         pw, ldw, relu, nullptr, stream);
+}
+
+extern "C" int avsd_convnd_ld_f32(const float* x, int ldx, const float* w, const float* bias, const float* res, const float* rscale,
+                                  float* out, int ldy, int n, int ti, int hi, int wi, int cin, int to, int ho, int wo, int cout, int kt,
+                                  int kh, int kw, int st, int sh, int sw, int pt, int ph, int pw, int ldw, int relu, void* stream) {
+  const ConvLd ld{ldx, ldy};
+  return convnd_dispatch("convnd_ld_f32", x, w, bias, res, rscale, out, n, ti, hi, wi, cin, to, ho, wo, cout, kt, kh, kw, st, sh, sw, pt,
+                         ph, pw, ldw, relu, &ld, stream);
 }
 
 extern "C" int avsd_maxpool_hw_f32(const float* x, float* out, int n_img, int hi, int wi, int c, int ho, int wo, void* stream) {
@@ -304,6 +395,28 @@ extern "C" int avsd_maxpool_hw_f32(const float* x, float* out, int n_img, int hi
   hipLaunchKernelGGL(maxpool_hw_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x,
                      out, hi, wi, c / 4, ho, wo, total);
   AVSD_CHECK_LAUNCH("maxpool_hw_f32 launch");
+  return AVSD_OK;
+}
+
+extern "C" int avsd_pool3_hw_f32(const float* x, int ldx, float* out, int ldy, int n_img, int hi, int wi, int c, int ho, int wo,
+                                 int stride, int pad, int avg, void* stream) {
+  AVSD_REQUIRE(x && out, "pool3_hw_f32: null pointer");
+  AVSD_REQUIRE(n_img > 0 && hi > 0 && wi > 0 && c > 0 && c % 4 == 0, "pool3_hw_f32: sizes must be positive, channels a multiple of 4");
+  AVSD_REQUIRE((stride == 2 && pad == 0) || (stride == 1 && pad == 1), "pool3_hw_f32: (stride, padding) must be (2, 0) or (1, 1), got (%d, %d)",
+               stride, pad);
+  AVSD_REQUIRE(hi + 2 * pad >= 3 && wi + 2 * pad >= 3, "pool3_hw_f32: the window does not fit the padded input (%d, %d)", hi, wi);
+  AVSD_REQUIRE(ho == (hi + 2 * pad - 3) / stride + 1 && wo == (wi + 2 * pad - 3) / stride + 1,
+               "pool3_hw_f32: output size (%d, %d) does not follow from input (%d, %d), stride %d and padding %d", ho, wo, hi, wi, stride, pad);
+  AVSD_REQUIRE(ldx >= c && ldy >= c && ldx % 4 == 0 && ldy % 4 == 0, "pool3_hw_f32: ldx %d and ldy %d must be at least c = %d and multiples of 4",
+               ldx, ldy, c);
+  AVSD_REQUIRE(((uintptr_t)x | (uintptr_t)out) % 16 == 0, "pool3_hw_f32: pointers must be 16-byte aligned");
+  const int64_t total = (int64_t)n_img * ho * wo * (c / 4);
+  AVSD_REQUIRE((total + 255) / 256 < (1ll << 31) && (int64_t)n_img * hi * wi < (1ll << 31), "pool3_hw_f32: tensor too large");
+  const dim3 grid((unsigned)((total + 255) / 256));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (avg) hipLaunchKernelGGL(pool3_hw_f32_kernel<true>, grid, dim3(256), 0, s, x, out, hi, wi, c / 4, ldx, ldy, ho, wo, stride, pad, total);
+  else hipLaunchKernelGGL(pool3_hw_f32_kernel<false>, grid, dim3(256), 0, s, x, out, hi, wi, c / 4, ldx, ldy, ho, wo, stride, pad, total);
+  AVSD_CHECK_LAUNCH("pool3_hw_f32 launch");
   return AVSD_OK;
 }
 

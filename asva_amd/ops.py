@@ -1361,6 +1361,77 @@ def maxpool_hw_f32(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _slice_ld(t: torch.Tensor, name: str) -> int:
+    """t [n, a, h, w, c]: a channel slice of a contiguous channels-last buffer [n, a, h, w, ld] (or the whole of it); -> ld"""
+    if t.dtype != F32 or not t.is_cuda or t.dim() != 5:
+        raise ValueError(f"{name} must be a 5-d f32 device tensor [n, t, h, w, c]")
+    n, a, h, w, c = t.shape
+    ld = t.stride(3) if n * a * h * w > 1 else max(t.stride(3), c)
+    want = (a * h * w * ld, h * w * ld, w * ld, ld, 1)
+    if ld < c or any(t.shape[i] > 1 and t.stride(i) != want[i] for i in range(5)):
+        raise ValueError(f"{name} {tuple(t.shape)} with strides {tuple(t.stride())} is not a channel slice of a contiguous channels-last buffer")
+    return ld
+
+
+def convnd_ld_f32(x: torch.Tensor, w: torch.Tensor, taps, stride, pad, *, out: Optional[torch.Tensor] = None,
+                  bias: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None, rscale: Optional[torch.Tensor] = None,
+                  relu: bool = False, ldx: Optional[int] = None, ldy: Optional[int] = None) -> torch.Tensor:
+    """convnd_f32 on channel slices: x [n, t, h, w, cin] may be a view x_wide[..., a:a + cin] of a contiguous channels-last buffer, and
+    `out`, if given, a view out_wide[..., b:b + cout] that the result is written into (columns outside it are not touched).  `res` has
+    the shape and the pixel stride of out.  ldx / ldy, if given, replace the pixel strides read from the views by smaller ones; see
+    avsd_convnd_ld_f32"""
+    for t, name in ((w, "w"), (bias, "bias"), (rscale, "rscale")):
+        if t is not None and (t.dtype != F32 or not t.is_cuda or not t.is_contiguous()):
+            raise ValueError(f"convnd_ld_f32: {name} must be a contiguous f32 device tensor")
+    if w.dim() != 2:
+        raise ValueError("convnd_ld_f32: w must be [cout, ldw]")
+    sx = _slice_ld(x, "convnd_ld_f32: x")
+    if ldx is not None and ldx > sx:
+        raise ValueError(f"convnd_ld_f32: ldx {ldx} is wider than the pixel stride {sx} of x")
+    ldx = sx if ldx is None else int(ldx)
+    n, ti, hi, wi, cin = x.shape
+    cout, ldw = w.shape
+    (kt, kh, kw), (st, sh, sw), (pt, ph, pw) = taps, stride, pad
+    to, ho, wo = (ti + 2 * pt - kt) // st + 1, (hi + 2 * ph - kh) // sh + 1, (wi + 2 * pw - kw) // sw + 1
+    if min(to, ho, wo) < 1:
+        raise ValueError(f"convnd_ld_f32: input {(ti, hi, wi)} is smaller than the window {tuple(taps)}")
+    if any(v is not None and v.numel() != cout for v in (bias, rscale)):
+        raise ValueError("convnd_ld_f32: bias / rscale must have cout entries")
+    if out is None:
+        out = torch.empty((n, to, ho, wo, cout), dtype=F32, device=x.device)
+    elif tuple(out.shape) != (n, to, ho, wo, cout):
+        raise ValueError(f"convnd_ld_f32: out {tuple(out.shape)} does not match {(n, to, ho, wo, cout)}")
+    sy = _slice_ld(out, "convnd_ld_f32: out")
+    if ldy is not None and ldy > sy:
+        raise ValueError(f"convnd_ld_f32: ldy {ldy} is wider than the pixel stride {sy} of out")
+    ldy = sy if ldy is None else int(ldy)
+    if res is not None and (tuple(res.shape) != tuple(out.shape) or _slice_ld(res, "convnd_ld_f32: res") != sy):
+        raise ValueError(f"convnd_ld_f32: res must have the shape {tuple(out.shape)} and the pixel stride {sy} of out")
+    check(_lib.lib().avsd_convnd_ld_f32(_p(x), ldx, _p(w), _p(bias), _p(res), _p(rscale), _p(out), ldy, n, ti, hi, wi, cin, to, ho, wo, cout,
+                                        kt, kh, kw, st, sh, sw, pt, ph, pw, ldw, int(relu), _stream()), "avsd_convnd_ld_f32")
+    return out
+
+
+def pool3_hw_f32(x: torch.Tensor, mode: str, stride: int, pad: int, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """3 x 3 pool on [n, t, h, w, c] (each of the n * t images on its own), mode "max" or "avg" (padded positions not counted),
+    (stride, pad) = (2, 0) or (1, 1); x and `out` may be channel slices as in convnd_ld_f32; see avsd_pool3_hw_f32"""
+    if mode not in ("max", "avg"):
+        raise ValueError(f"pool3_hw_f32: mode {mode!r}")
+    ldx = _slice_ld(x, "pool3_hw_f32: x")
+    n, t, hi, wi, c = x.shape
+    ho, wo = (hi + 2 * pad - 3) // stride + 1, (wi + 2 * pad - 3) // stride + 1
+    if min(ho, wo) < 1:
+        raise ValueError(f"pool3_hw_f32: input {(hi, wi)} is smaller than the window")
+    if out is None:
+        out = torch.empty((n, t, ho, wo, c), dtype=F32, device=x.device)
+    elif tuple(out.shape) != (n, t, ho, wo, c):
+        raise ValueError(f"pool3_hw_f32: out {tuple(out.shape)} does not match {(n, t, ho, wo, c)}")
+    ldy = _slice_ld(out, "pool3_hw_f32: out")
+    check(_lib.lib().avsd_pool3_hw_f32(_p(x), ldx, _p(out), ldy, n * t, hi, wi, c, ho, wo, int(stride), int(pad), int(mode == "avg"),
+                                       _stream()), "avsd_pool3_hw_f32")
+    return out
+
+
 def mean_rows_f32(x: torch.Tensor) -> torch.Tensor:
     """[n, ..., c] -> [n, c]: mean over all positions of a sample"""
     _req(x, F32, "x")

@@ -464,6 +464,23 @@ int avsd_gemm_f32(const float* A, int lda, const float* W, int ldw, const float*
 int avsd_convnd_f32(const float* x, const float* w, const float* bias, const float* res, const float* rscale, float* out,
                     int n, int ti, int hi, int wi, int cin, int to, int ho, int wo, int cout, int kt, int kh, int kw,
                     int st, int sh, int sw, int pt, int ph, int pw, int ldw, int relu, void* stream);
+/* avsd_convnd_f32 on channel slices of wider channels-last buffers: consecutive pixels of x are ldx >= cin elements apart, those of
+ * out ldy >= cout, and x / out point at the first channel of their slice.  res, if given, is addressed with ldy as well (it has the
+ * layout of out).  A branch of an Inception block (asva_amd/fid.py) writes straight into its slice of the block's concatenated
+ * output, and a convolution reads its slice of what a stacked 1 x 1 convolution produced: there is no concat or copy kernel.
+ * Channels >= cin of an input pixel are never read and columns >= cout of an output row never written.  The arithmetic is that of
+ * avsd_convnd_f32 bit for bit (the same chain per output element; only addresses differ).  The float4 loader is taken when
+ * cin % 32 == 0, ldw % 4 == 0, ldx % 4 == 0 and x, w are 16-byte aligned; any other slice falls back to the scalar loader, which
+ * gives the same bits. */
+int avsd_convnd_ld_f32(const float* x, int ldx, const float* w, const float* bias, const float* res, const float* rscale, float* out,
+                       int ldy, int n, int ti, int hi, int wi, int cin, int to, int ho, int wo, int cout, int kt, int kh, int kw,
+                       int st, int sh, int sw, int pt, int ph, int pw, int ldw, int relu, void* stream);
+/* The 3 x 3 pools of Inception-v3 on [n_img][hi][wi][c] -> [n_img][ho][wo][c], pixels ldx / ldy elements apart (channel slices as
+ * above; c, ldx, ldy multiples of 4, pointers 16-byte aligned).  (stride, pad) is (2, 0) or (1, 1) and the output size must follow
+ * from it.  avg = 0: maximum, exact; padded positions do not take part (F.max_pool2d).  avg = 1: the taps inside the image summed in
+ * (dy, dx) order, divided by their number 4, 6 or 9 (F.avg_pool2d(count_include_pad=False), inception_v3.py:228). */
+int avsd_pool3_hw_f32(const float* x, int ldx, float* out, int ldy, int n_img, int hi, int wi, int c, int ho, int wo, int stride,
+                      int pad, int avg, void* stream);
 /* nn.MaxPool3d((1,3,3), stride (1,2,2), padding (0,1,1)) (video.py:62) on [n_img][hi][wi][c] -> [n_img][ho][wo][c]; padded
  * positions do not take part.  c a multiple of 4. */
 int avsd_maxpool_hw_f32(const float* x, float* out, int n_img, int hi, int wi, int c, int ho, int wo, void* stream);
