@@ -656,30 +656,12 @@ def test_cross_attention_block_matches_separate_kernels_and_fp32(ops, kind, lk, 
     """avsd_cross_attention_block (one launch) against (a) the three kernels it replaces — LayerNorm-folded Q projection,
     attention over the gathered keys, output projection + residual — and (b) a plain fp32 statement of
     h + to_out(softmax(LN(h) Wq K^T / sqrt(d)) V).  C = 320, 8 heads of 40, 2 clips x 3 frames x 256 rows."""
-    torch.manual_seed(0)
-    B, Fr, L, C, heads = 2, 3, 256, 320, 8
-    d = C // heads
-    M = B * Fr * L
-    a0 = rnd(M, C, seed=1)
-    w0 = rnd(C, C, seed=2, scale=C ** -0.5)
-    res0 = rnd(M, C, seed=3) + 0.5
-    stats = torch.empty(M, C // 32, 2, device=dev())
-    h = ops.gemm(a0, w0, res1=res0, rowstats=stats)                     # residual stream + its LayerNorm statistics
-    gamma, beta = 1 + 0.1 * rndf(C, seed=4), 0.1 * rndf(C, seed=5)
-    wq = rndf(C, C, seed=6, scale=C ** -0.5)
-    wq_f = (wq * gamma[None, :]).to(torch.bfloat16)
-    q_colsum, q_bias = wq_f.float().sum(1), wq @ beta
-    wo, bo = rnd(C, C, seed=7, scale=C ** -0.5), rndf(C, seed=8)
-    nkv = B * Fr if per_frame else B
-    lkp = (lk + 31) // 32 * 32
-    kk, vv = rnd(nkv, lk, C, seed=9), rnd(nkv, lk, C, seed=10)
-    k_pad = torch.zeros(nkv, lkp, C, dtype=torch.bfloat16, device=dev())
-    vt_pad = torch.zeros(nkv, C, lkp, dtype=torch.bfloat16, device=dev())
-    k_pad[:, :lk] = kk
-    vt_pad[:, :, :lk] = vv.transpose(1, 2)
-    q_per_kv = 1 if per_frame else Fr
-    master_in = h.float() + 1e-3 * rndf(M, C, seed=11) if f32_res else None      # an f32 master that differs from its 16-bit copy
-    res = master_in if f32_res else h
+    from tests.helpers import xattn_block_operands
+
+    p = xattn_block_operands(ops, torch.bfloat16, lk, per_frame, f32_res)
+    B, Fr, L, C, heads, d, M = p.B, p.Fr, p.L, p.C, p.heads, p.d, p.M
+    h, stats, gamma, beta, wq, wq_f, q_colsum, q_bias, wo, bo = p.h, p.stats, p.gamma, p.beta, p.wq, p.wq_f, p.q_colsum, p.q_bias, p.wo, p.bo
+    nkv, kk, vv, k_pad, vt_pad, q_per_kv, res = p.nkv, p.kk, p.vv, p.k_pad, p.vt_pad, p.q_per_kv, p.res
     stats_out = torch.empty_like(stats)
     master = torch.empty(M, C, device=dev()) if f32_res else None
     out = ops.cross_attention_block(h, stats, wq_f, q_colsum, q_bias, k_pad, vt_pad, lk, wo, bo, res=res, heads=heads, L=L,
