@@ -135,6 +135,8 @@ SIGNATURES = {
     "avsd_convnd_f32": (c_int, [c_void_p] * 6 + [c_int] * 20 + [c_void_p]),
     "avsd_convnd_ld_f32": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int] * 21 + [c_void_p]),
     "avsd_pool3_hw_f32": (c_int, [c_void_p, c_int, c_void_p, c_int] + [c_int] * 9 + [c_void_p]),
+    "avsd_conv3d_same_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int] + [c_int] * 18 + [c_void_p]),
+    "avsd_maxpool3d_same_f32": (c_int, [c_void_p, c_int, c_void_p, c_int] + [c_int] * 14 + [c_void_p]),
     "avsd_maxpool_hw_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "avsd_mean_rows_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "avsd_resize_aa_normalize_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,

@@ -4,7 +4,8 @@
 // measures, so NOTHING here uses the 16-bit type of the build: tensors are f32, products run on the f32-input matrix cores
 // (v_mfma_f32_32x32x2_f32, as csrc/gemm_f32.hip), and the bf16 and fp16 libraries compile this file to the same arithmetic.
 // Also here, because they share the convolution body: the two kernels Inception-v3 adds for FID (asva_amd/fid.py) — the convolution
-// on channel slices of wider buffers (avsd_convnd_ld_f32) and the 3 x 3 pools (avsd_pool3_hw_f32).
+// on channel slices of wider buffers (avsd_convnd_ld_f32) and the 3 x 3 pools (avsd_pool3_hw_f32) — and the two kernels I3D adds for
+// FVD (asva_amd/fvd.py): the same convolution with "same" padding (avsd_conv3d_same_f32) and the 3-D max pool (avsd_maxpool3d_same_f32).
 //
 // Layout: channels-last f32, video activations [n][t][h][w][c], audio activations the same with t = 1.
 #include "avsd_common.h"
@@ -30,17 +31,29 @@ struct ConvLd {
   int ldx, ldy;
 };
 
+// four consecutive floats at an address that is only 4-byte aligned (the run loader): one global_load_dwordx4
+struct __attribute__((packed, aligned(4))) F4U {
+  float x, y, z, w;
+};
+
 // LD = false: pixels are cin / cout elements apart (avsd_convnd_f32); LD = true: ld.ldx / ld.ldy apart.  Only addresses differ:
 // the chain of every output element is the same in both.
-template <int FM, int FN, bool VEC, bool LD>
+// RUN (avsd_conv3d_same_f32 with a small cin and ldx == cin): the kw * cin floats that one (dt, dh) row of the window reads are
+// contiguous in memory and in k.  A thread owns four consecutive k as in the float4 loader; where they lie in one run and inside
+// the image it fetches them with one 4-byte-aligned wide load, anywhere else (a run boundary, the w borders, the K tail) element by
+// element as the scalar loader does.  For x a half wave holds ONE group of four k and 32 rows, so that whether the group straddles a
+// run is uniform across it and most waves never enter the element-wise path; neighbouring rows read overlapping addresses (stride *
+// cin floats apart).  The LDS tiles hold the same values in the same places for all three loaders.
+template <int FM, int FN, bool VEC, bool LD, bool RUN = false>
 __device__ __forceinline__ void convnd_f32_body(const float* __restrict__ x, const float* __restrict__ w,
                                                 const float* __restrict__ bias, const float* __restrict__ res,
                                                 const float* __restrict__ rscale, float* __restrict__ out, const ConvGeom& g,
                                                 const ConvLd& ld) {
   const int ldx = LD ? ld.ldx : g.cin, ldy = LD ? ld.ldy : g.cout;
   constexpr int BM = 64 * FM, BN = 64 * FN;
-  constexpr int NA = VEC ? BM / 32 : BM / 8;      // A elements (float4 / float) each thread fetches per K tile
-  constexpr int NW = VEC ? BN / 32 : BN / 8;
+  constexpr bool V4 = VEC || RUN;                 // four consecutive k per thread
+  constexpr int NA = V4 ? BM / 32 : BM / 8;       // A elements (float4 / float) each thread fetches per K tile
+  constexpr int NW = V4 ? BN / 32 : BN / 8;
   __shared__ float sA[BM * CP];
   __shared__ float sW[BN * CP];
   __shared__ int4 sRow[BM];                        // per tile row: (sample n, to*st - pt, ho*sh - ph, wo*sw - pw)
@@ -73,13 +86,65 @@ __device__ __forceinline__ void convnd_f32_body(const float* __restrict__ x, con
 
   // VEC (cin % 32 == 0, so a K tile lies inside one tap): thread = (row lr of a 32-row slab, float4 at channel lk)
   // else: thread = (k column tid & 31, row tid >> 5 of an 8-row slab), one float at a time, tap decoded per element
-  const int lr = VEC ? tid >> 3 : tid >> 5;
-  const int lk = VEC ? (tid & 7) * 4 : tid & 31;
-  float4 ra[VEC ? NA : 1], rw[VEC ? NW : 1];
-  float fa[VEC ? 1 : NA], fw[VEC ? 1 : NW];
+  const int lr = V4 ? tid >> 3 : tid >> 5;
+  const int lk = V4 ? (tid & 7) * 4 : tid & 31;
+  const int ar = RUN ? tid & 31 : lr;             // the x tile of the run loader: (row ar of a 32-row slab, four k at ak)
+  const int ak = RUN ? (tid >> 5) * 4 : lk;
+  float4 ra[V4 ? NA : 1], rw[V4 ? NW : 1];
+  float fa[V4 ? 1 : NA], fw[V4 ? 1 : NW];
 
   auto fetch = [&](int k0) {
-    if constexpr (VEC) {
+    if constexpr (RUN) {
+      const int k = k0 + ak;
+      int edt[4], edh[4], edw[4], ec[4];
+      bool ek[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        ek[e] = k + e < K;
+        const int tap = (k + e) / g.cin;
+        ec[e] = k + e - tap * g.cin;
+        edw[e] = tap % g.kw;
+        edh[e] = (tap / g.kw) % g.kh;
+        edt[e] = tap / (g.kw * g.kh);
+      }
+      // the four k lie in one (dt, dh) row of the window: consecutive floats of x (pixels are cin apart here)
+      const bool whole = ek[3] && edt[3] == edt[0] && edh[3] == edh[0];
+#pragma unroll
+      for (int i = 0; i < NA; ++i) {
+        const int4 rv = sRow[ar + 32 * i];
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        const int t0 = rv.y + edt[0], h0 = rv.z + edh[0];
+        if (whole && (unsigned)t0 < (unsigned)g.ti && (unsigned)h0 < (unsigned)g.hi && rv.w + edw[0] >= 0 && rv.w + edw[3] < g.wi) {
+          const F4U q = *reinterpret_cast<const F4U*>(x + ((((int64_t)rv.x * g.ti + t0) * g.hi + h0) * g.wi + rv.w + edw[0]) * g.cin + ec[0]);
+          v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int t = rv.y + edt[e], h = rv.z + edh[e], ww = rv.w + edw[e];
+            if (ek[e] && (unsigned)t < (unsigned)g.ti && (unsigned)h < (unsigned)g.hi && (unsigned)ww < (unsigned)g.wi)
+              v[e] = x[((((int64_t)rv.x * g.ti + t) * g.hi + h) * g.wi + ww) * g.cin + ec[e]];
+          }
+        }
+        ra[i] = make_float4(v[0], v[1], v[2], v[3]);
+      }
+#pragma unroll
+      for (int i = 0; i < NW; ++i) {
+        const int nn = n0 + lr + 32 * i;
+        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (nn < g.cout) {
+          const int kw0 = k0 + lk;
+          const float* pw = w + (int64_t)nn * g.ldw + kw0;
+          if (kw0 + 3 < K) {
+            q = *reinterpret_cast<const float4*>(pw);
+          } else {                    // the K tail: columns >= K of a weight row are never read
+            if (kw0 < K) q.x = pw[0];
+            if (kw0 + 1 < K) q.y = pw[1];
+            if (kw0 + 2 < K) q.z = pw[2];
+          }
+        }
+        rw[i] = q;
+      }
+    } else if constexpr (VEC) {
       const int tap = k0 / g.cin, c = k0 - tap * g.cin + lk;
       const int dw = tap % g.kw, dh = (tap / g.kw) % g.kh, dt = tap / (g.kw * g.kh);
 #pragma unroll
@@ -115,10 +180,10 @@ __device__ __forceinline__ void convnd_f32_body(const float* __restrict__ x, con
     }
   };
   auto stage = [&]() {
-    if constexpr (VEC) {
+    if constexpr (V4) {
 #pragma unroll
       for (int i = 0; i < NA; ++i) {
-        float* d = sA + (lr + 32 * i) * CP + lk;
+        float* d = sA + (ar + 32 * i) * CP + ak;
         d[0] = ra[i].x; d[1] = ra[i].y; d[2] = ra[i].z; d[3] = ra[i].w;
       }
 #pragma unroll
@@ -243,6 +308,65 @@ int convnd_dispatch(const char* who, const float* x, const float* w, const float
   }
   AVSD_CHECK_LAUNCH(ld ? "convnd_ld_f32 launch" : "convnd_f32 launch");
   return AVSD_OK;
+}
+
+// ---- avsd_conv3d_same_f32 (asva_amd/fvd.py): the body above with TensorFlow "same" zero padding worked out here from input size,
+// window and stride.  Only the padding in front enters the geometry: every tap is bounds-checked, and the padding behind is those
+// checks.  LOADER 1 scalar, 2 float4, 3 run; the chain of every output element is the same for all of them. ---------------------------
+template <int FM, int FN, int LOADER>
+__global__ __launch_bounds__(256) void conv3d_same_f32_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                              const float* __restrict__ bias, float* __restrict__ out, ConvGeom g,
+                                                              ConvLd ld) {
+  convnd_f32_body<FM, FN, LOADER == 2, true, LOADER == 3>(x, w, bias, nullptr, nullptr, out, g, ld);
+}
+
+template <int FM, int FN>
+void launch_conv_same(int loader, dim3 grid, hipStream_t s, const float* x, const float* w, const float* bias, float* out,
+                      const ConvGeom& g, const ConvLd& ld) {
+  if (loader == 3) hipLaunchKernelGGL((conv3d_same_f32_kernel<FM, FN, 3>), grid, dim3(256), 0, s, x, w, bias, out, g, ld);
+  else if (loader == 2) hipLaunchKernelGGL((conv3d_same_f32_kernel<FM, FN, 2>), grid, dim3(256), 0, s, x, w, bias, out, g, ld);
+  else hipLaunchKernelGGL((conv3d_same_f32_kernel<FM, FN, 1>), grid, dim3(256), 0, s, x, w, bias, out, g, ld);
+}
+
+// TensorFlow "same": the total padding of one axis; pad / 2 of it goes in front, the rest behind; the output is ceil(size / stride)
+inline int same_pad_total(int size, int k, int s) {
+  const int r = size % s;
+  const int p = k - (r == 0 ? s : r);
+  return p > 0 ? p : 0;
+}
+
+// ---- avsd_maxpool3d_same_f32: window 1 .. 3 and stride 1 .. 2 per axis, "same" padding; one thread per output position and 4
+// channels.  A padded position takes part in the maximum as 0.0f (the reference pads with F.pad, then pools unpadded). ------------------
+struct PoolGeom {
+  int ti, hi, wi, c4, to, ho, wo, ldx, ldy;
+  int kt, kh, kw, st, sh, sw, pt, ph, pw;
+};
+__global__ __launch_bounds__(256) void maxpool3d_same_f32_kernel(const float* __restrict__ x, float* __restrict__ out, PoolGeom g,
+                                                                 int64_t total) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int c = (int)(idx % g.c4);
+  int64_t q = idx / g.c4;
+  const int ox = (int)(q % g.wo); q /= g.wo;
+  const int oy = (int)(q % g.ho); q /= g.ho;
+  const int ot = (int)(q % g.to);
+  const int64_t n = q / g.to;
+  const float* src = x + n * g.ti * g.hi * g.wi * g.ldx + 4 * c;
+  float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+  for (int dt = 0; dt < g.kt; ++dt) {
+    const int t = ot * g.st - g.pt + dt;
+    for (int dy = 0; dy < g.kh; ++dy) {
+      const int y = oy * g.sh - g.ph + dy;
+      for (int dx = 0; dx < g.kw; ++dx) {
+        const int xx = ox * g.sw - g.pw + dx;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if ((unsigned)t < (unsigned)g.ti && (unsigned)y < (unsigned)g.hi && (unsigned)xx < (unsigned)g.wi)
+          v = *reinterpret_cast<const float4*>(src + (((int64_t)t * g.hi + y) * g.wi + xx) * g.ldx);
+        m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+      }
+    }
+  }
+  *reinterpret_cast<float4*>(out + (((n * g.to + ot) * g.ho + oy) * g.wo + ox) * g.ldy + 4 * c) = m;
 }
 
 // ---- avsd_maxpool_hw_f32: (1, 3, 3) window, stride (1, 2, 2), padding (0, 1, 1); one thread per output pixel and 4 channels ---------
@@ -382,6 +506,76 @@ extern "C" int avsd_convnd_ld_f32(const float* x, int ldx, const float* w, const
   const ConvLd ld{ldx, ldy};
   return convnd_dispatch("convnd_ld_f32", x, w, bias, res, rscale, out, n, ti, hi, wi, cin, to, ho, wo, cout, kt, kh, kw, st, sh, sw, pt,
                          ph, pw, ldw, relu, &ld, stream);
+}
+
+extern "C" int avsd_conv3d_same_f32(const float* x, int ldx, const float* w, const float* bias, float* out, int ldy, int n, int ti, int hi,
+                                    int wi, int cin, int to, int ho, int wo, int cout, int kt, int kh, int kw, int st, int sh, int sw,
+                                    int ldw, int relu, int loader, void* stream) {
+  AVSD_REQUIRE(x && w && out, "conv3d_same_f32: null pointer");
+  AVSD_REQUIRE(n > 0 && ti > 0 && hi > 0 && wi > 0 && cin > 0 && cout > 0, "conv3d_same_f32: sizes must be positive");
+  AVSD_REQUIRE(kt > 0 && kh > 0 && kw > 0 && kt <= 16 && kh <= 16 && kw <= 16 && st > 0 && sh > 0 && sw > 0,
+               "conv3d_same_f32: taps must be 1 .. 16 and strides positive");
+  AVSD_REQUIRE(to == (ti + st - 1) / st && ho == (hi + sh - 1) / sh && wo == (wi + sw - 1) / sw,
+               "conv3d_same_f32: output size (%d, %d, %d) is not ceil(input / stride) of input (%d, %d, %d) and stride (%d, %d, %d)", to, ho,
+               wo, ti, hi, wi, st, sh, sw);
+  const int64_t K64 = (int64_t)kt * kh * kw * cin, M64 = (int64_t)n * to * ho * wo;
+  AVSD_REQUIRE(ldw >= K64, "conv3d_same_f32: ldw %d is smaller than K = taps * cin = %lld", ldw, (long long)K64);
+  AVSD_REQUIRE(M64 < (1ll << 31) && K64 < (1ll << 24) && (int64_t)n * ti * hi * wi < (1ll << 31), "conv3d_same_f32: tensor too large");
+  AVSD_REQUIRE(ldx >= cin, "conv3d_same_f32: ldx %d is smaller than cin %d", ldx, cin);
+  AVSD_REQUIRE(ldy >= cout, "conv3d_same_f32: ldy %d is smaller than cout %d", ldy, cout);
+  const bool w4 = ldw % 4 == 0 && (uintptr_t)w % 16 == 0;
+  const bool can_vec = w4 && cin % CK == 0 && ldx % 4 == 0 && (uintptr_t)x % 16 == 0;
+  const bool can_run = w4 && ldx == cin;       // pixels side by side: a (dt, dh) row of the window is one run of kw * cin floats
+  AVSD_REQUIRE(loader >= 0 && loader <= 3, "conv3d_same_f32: loader must be 0 (automatic), 1 (scalar), 2 (float4) or 3 (run), got %d", loader);
+  AVSD_REQUIRE(loader != 2 || can_vec,
+               "conv3d_same_f32: loader 2 (float4) needs cin %% 32 == 0, ldx %% 4 == 0, ldw %% 4 == 0 and 16-byte aligned x and w");
+  AVSD_REQUIRE(loader != 3 || can_run, "conv3d_same_f32: loader 3 (run) needs ldx == cin, ldw %% 4 == 0 and a 16-byte aligned w");
+  // measured on the stem (cin 3, K 1029, 8 clips of 12 x 224 x 224): scalar 1.26 ms, run 1.29 ms — the layer is bound by its 128 x 64
+  // tile, not by its loads (profiles/fvd.md), so the run loader is never picked; it stays selectable for A/Bs
+  if (loader == 0) loader = can_vec ? 2 : 1;
+  ConvGeom g{n, ti, hi, wi, cin, to, ho, wo, cout, kt, kh, kw, st, sh, sw, same_pad_total(ti, kt, st) / 2, same_pad_total(hi, kh, sh) / 2,
+             same_pad_total(wi, kw, sw) / 2, ldw, relu ? 1 : 0, (int)M64, (int)K64};
+  const ConvLd ld{ldx, ldy};
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  // the tile rule of avsd_convnd_f32 (the result does not depend on it)
+  const int fn = cout <= 64 ? 1 : 2;
+  const int64_t big = ((M64 + 127) / 128) * ((cout + 64 * fn - 1) / (64 * fn));
+  if (big < 256) {
+    dim3 grid((unsigned)((cout + 63) / 64), (unsigned)((M64 + 63) / 64));
+    launch_conv_same<1, 1>(loader, grid, s, x, w, bias, out, g, ld);
+  } else if (fn == 1) {
+    dim3 grid((unsigned)((cout + 63) / 64), (unsigned)((M64 + 127) / 128));
+    launch_conv_same<2, 1>(loader, grid, s, x, w, bias, out, g, ld);
+  } else {
+    dim3 grid((unsigned)((cout + 127) / 128), (unsigned)((M64 + 127) / 128));
+    launch_conv_same<2, 2>(loader, grid, s, x, w, bias, out, g, ld);
+  }
+  AVSD_CHECK_LAUNCH("conv3d_same_f32 launch");
+  return AVSD_OK;
+}
+
+extern "C" int avsd_maxpool3d_same_f32(const float* x, int ldx, float* out, int ldy, int n, int ti, int hi, int wi, int c, int to, int ho,
+                                       int wo, int kt, int kh, int kw, int st, int sh, int sw, void* stream) {
+  AVSD_REQUIRE(x && out, "maxpool3d_same_f32: null pointer");
+  AVSD_REQUIRE(n > 0 && ti > 0 && hi > 0 && wi > 0 && c > 0 && c % 4 == 0, "maxpool3d_same_f32: sizes must be positive, channels a multiple of 4");
+  AVSD_REQUIRE(kt >= 1 && kh >= 1 && kw >= 1 && kt <= 3 && kh <= 3 && kw <= 3, "maxpool3d_same_f32: windows must be 1 .. 3, got (%d, %d, %d)", kt,
+               kh, kw);
+  AVSD_REQUIRE(st >= 1 && sh >= 1 && sw >= 1 && st <= 2 && sh <= 2 && sw <= 2, "maxpool3d_same_f32: strides must be 1 .. 2, got (%d, %d, %d)", st,
+               sh, sw);
+  AVSD_REQUIRE(to == (ti + st - 1) / st && ho == (hi + sh - 1) / sh && wo == (wi + sw - 1) / sw,
+               "maxpool3d_same_f32: output size (%d, %d, %d) is not ceil(input / stride) of input (%d, %d, %d) and stride (%d, %d, %d)", to,
+               ho, wo, ti, hi, wi, st, sh, sw);
+  AVSD_REQUIRE(ldx >= c && ldy >= c && ldx % 4 == 0 && ldy % 4 == 0,
+               "maxpool3d_same_f32: ldx %d and ldy %d must be at least c = %d and multiples of 4", ldx, ldy, c);
+  AVSD_REQUIRE(((uintptr_t)x | (uintptr_t)out) % 16 == 0, "maxpool3d_same_f32: pointers must be 16-byte aligned");
+  const int64_t total = (int64_t)n * to * ho * wo * (c / 4);
+  AVSD_REQUIRE((total + 255) / 256 < (1ll << 31) && (int64_t)n * ti * hi * wi < (1ll << 31), "maxpool3d_same_f32: tensor too large");
+  const PoolGeom g{ti, hi, wi, c / 4, to, ho, wo, ldx, ldy, kt, kh, kw, st, sh, sw, same_pad_total(ti, kt, st) / 2,
+                   same_pad_total(hi, kh, sh) / 2, same_pad_total(wi, kw, sw) / 2};
+  hipLaunchKernelGGL(maxpool3d_same_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x,
+                     out, g, total);
+  AVSD_CHECK_LAUNCH("maxpool3d_same_f32 launch");
+  return AVSD_OK;
 }
 
 extern "C" int avsd_maxpool_hw_f32(const float* x, float* out, int n_img, int hi, int wi, int c, int ho, int wo, void* stream) {

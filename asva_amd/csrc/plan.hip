@@ -77,6 +77,8 @@ const Entry kEntries[] = {
     AVSD_PLAN_ENTRY(avsd_resize_aa_normalize_f32),
     // Inception-v3 features for FID (asva_amd/fid.py; kernels in csrc/avsync.hip)
     AVSD_PLAN_ENTRY(avsd_convnd_ld_f32),    AVSD_PLAN_ENTRY(avsd_pool3_hw_f32),
+    // I3D features for FVD (asva_amd/fvd.py; kernels in csrc/avsync.hip)
+    AVSD_PLAN_ENTRY(avsd_conv3d_same_f32),  AVSD_PLAN_ENTRY(avsd_maxpool3d_same_f32),
     // CLIP text encoder (csrc/clip_text.hip)
     AVSD_PLAN_ENTRY(avsd_embed_tokens_f32), AVSD_PLAN_ENTRY(avsd_layernorm_f32),         AVSD_PLAN_ENTRY(avsd_attention_causal_f32),
     AVSD_PLAN_ENTRY(avsd_quick_gelu_f32),

@@ -1,5 +1,5 @@
 """The reference's evaluation driver (avgen/evaluations/eval.py:28-281) over the device metrics of this package: FID
-(asva_amd.fid), IA / IT (asva_amd.imagebind_eval), RelSync (asva_amd.avsync) and AlignSync.  FVD (I3D) is not implemented.
+(asva_amd.fid), FVD (asva_amd.fvd), IA / IT (asva_amd.imagebind_eval), RelSync (asva_amd.avsync) and AlignSync.
 
 `evaluate_generation_results` follows the reference step by step: the file-count assertion, groundtruth clips in sorted order, the
 generated clips of each in sorted order, the first frame excluded from FID, the same `result_dict` keys and JSON file.  Steps 4 and 5
@@ -18,8 +18,9 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
-FVD_MESSAGE = ("FVD is not implemented: the I3D network is not part of this package; pass eval_fvd=False "
-               "(FID, IA / IT, RelSync and AlignSync are available)")
+FVD_MESSAGE = ("FVD needs the I3D detector, which is never downloaded: pass models={'fvd': asva_amd.fvd.load_i3d_pretrained(weights=...)} "
+               "or set the environment variable AVSD_FVD_I3D to the path of i3d_torchscript.pt (or of a state dict), or pass eval_fvd=False "
+               "(FID, IA / IT, RelSync and AlignSync do not need it)")
 
 
 def _generated_paths(generated_video_root: str, groundtruth_video_name: str) -> List[str]:
@@ -34,10 +35,12 @@ def reduce_metrics(groundtruth_fid_features: Optional[Sequence[torch.Tensor]] = 
                    generated_avsync_scores: Optional[Sequence[torch.Tensor]] = None,
                    groundtruth_first_frame_ia_sims: Optional[Sequence[torch.Tensor]] = None,
                    generated_pred_frame_ia_sims: Optional[Sequence[torch.Tensor]] = None,
-                   generated_video_names: Optional[Sequence[str]] = None) -> Dict:
+                   generated_video_names: Optional[Sequence[str]] = None, *,
+                   groundtruth_fvd_features: Optional[Sequence[torch.Tensor]] = None,
+                   generated_fvd_features: Optional[Sequence[torch.Tensor]] = None) -> Dict:
     """eval.py:203-275 as a pure host function: lists of per-video / per-clip CPU tensors in, the metric entries of `result_dict` out.
     A metric is computed when its inputs are given: FID from (b, f, c) feature lists (first frame dropped), IA / IT from per-clip
-    means (b,), RelSync from raw classifier scores (b,), AlignSync from the (b, 1) first-frame and (b, f - 1) predicted-frame
+    means (b,), FVD from (b, c) feature lists (one row per clip, all frames), RelSync from raw classifier scores (b,), AlignSync from the (b, 1) first-frame and (b, f - 1) predicted-frame
     image-audio similarities together with RelSync.  `generated_video_names`, if given, adds "instance_metrics": one record per
     generated clip, in the order the lists were filled."""
     from .fid import frechet_distance
@@ -47,6 +50,8 @@ def reduce_metrics(groundtruth_fid_features: Optional[Sequence[torch.Tensor]] = 
         gt = torch.cat(list(groundtruth_fid_features))[:, 1:].flatten(end_dim=1)          # exclude the first frame: (B * (f - 1), c)
         gen = torch.cat(list(generated_fid_features))[:, 1:].flatten(end_dim=1)
         out["FID"] = frechet_distance(gt, gen).item()
+    if groundtruth_fvd_features is not None:
+        out["FVD"] = frechet_distance(torch.cat(list(groundtruth_fvd_features)), torch.cat(list(generated_fvd_features))).item()
     ias = its = relsync = alignsync = None
     if generated_ias is not None:
         ias, its = torch.cat(list(generated_ias)), torch.cat(list(generated_its))
@@ -85,15 +90,18 @@ def evaluate_generation_results(groundtruth_video_root: str, groundtruth_video_n
                                 eval_alignsync: bool = True, record_instance_metrics: bool = False, dtype: torch.dtype = torch.float32,
                                 models: Optional[Dict[str, torch.nn.Module]] = None) -> Dict:
     """eval.py:28-281.  `models` (not in the reference): preloaded nets under the keys "fid" (asva_amd.fid.InceptionV3 returning block
-    3 first), "avsync" (AVSyncClassifier) and "clip" (imagebind_eval.CLIPModel); a net that is needed and not given comes from its
-    default loader (load_inceptionv3_pretrained, load_avsync_model, load_clip_model), none of which downloads anything."""
-    if eval_fvd:
+    3 first), "fvd" (asva_amd.fvd.InceptionI3d), "avsync" (AVSyncClassifier) and "clip" (imagebind_eval.CLIPModel); a net that is needed
+    and not given comes from its default loader (load_inceptionv3_pretrained, load_i3d_pretrained, load_avsync_model, load_clip_model),
+    none of which downloads anything.  eval_fvd=True (the default, as in the reference) without models["fvd"] and without
+    $AVSD_FVD_I3D is refused before any file is read and before any other network is loaded."""
+    if eval_fvd and not (models or {}).get("fvd") and not os.environ.get("AVSD_FVD_I3D"):
         raise NotImplementedError(FVD_MESSAGE)
     if dtype != torch.float32:
         raise ValueError("the evaluation networks compute in float32 only")
     from .avsync import compute_avsync_scores, load_avsync_model
     from .data_utils import load_av_clips_uniformly
     from .fid import compute_fid_image_features, load_inceptionv3_pretrained
+    from .fvd import compute_fvd_video_features, load_i3d_pretrained
     from .imagebind_eval import compute_clip_consistency, load_clip_model
 
     device = torch.device("cuda")
@@ -110,13 +118,16 @@ def evaluate_generation_results(groundtruth_video_root: str, groundtruth_video_n
         assert eval_clipsim and eval_relsync
 
     # 1. models and feature lists
-    iv3_fid = clip_model = avsync_net = None
+    iv3_fid = i3d_fvd = clip_model = avsync_net = None
     if eval_fid:
         iv3_fid = (models.get("fid") or load_inceptionv3_pretrained(block_ids=[3], use_fid_inception=True)).to(device=device, dtype=dtype)
+    if eval_fvd:
+        i3d_fvd = (models.get("fvd") or load_i3d_pretrained()).to(device=device, dtype=dtype)
     if eval_clipsim:
         clip_model = (models.get("clip") or load_clip_model()).to(device=device, dtype=dtype)
     if eval_relsync:
         avsync_net = (models.get("avsync") or load_avsync_model()).to(device=device, dtype=dtype)
+    gt_fvd, gen_fvd = [], []
     gt_fid, gen_fid, gen_ias, gen_its, gt_scores, gen_scores, gt_first_ia, gen_pred_ia, gen_names = [], [], [], [], [], [], [], [], []
 
     def load(path, num_clips):
@@ -128,12 +139,17 @@ def evaluate_generation_results(groundtruth_video_root: str, groundtruth_video_n
         b, f = videos.shape[:2]
         return compute_fid_image_features(videos.flatten(end_dim=1), iv3_fid).detach().cpu().view(b, f, -1)
 
+    def fvd_features(videos):                                                   # all frames: the first one is not dropped (eval.py:118-123)
+        return compute_fvd_video_features(videos.permute(0, 2, 1, 3, 4), i3d_fvd).detach().cpu()      # b f c h w -> b c f h w; (b, c)
+
     # 2. groundtruth clips, in sorted order
     groundtruth_video_names.sort()
     for name, _category in zip(groundtruth_video_names, groundtruth_categories):
         videos, audios = load(os.path.join(groundtruth_video_root, name), num_clips_per_video)
         if eval_fid:
             gt_fid.append(fid_features(videos))
+        if eval_fvd:
+            gt_fvd.append(fvd_features(videos))
         if eval_alignsync:
             gt_first_ia.append(compute_clip_consistency(videos[:, 0:1], audios, net=clip_model)["ia_sim"].detach().cpu())      # (b, 1)
         if eval_relsync:
@@ -146,6 +162,8 @@ def evaluate_generation_results(groundtruth_video_root: str, groundtruth_video_n
             videos, audios = load(path, 1)
             if eval_fid:
                 gen_fid.append(fid_features(videos))
+            if eval_fvd:
+                gen_fvd.append(fvd_features(videos))
             if eval_clipsim:
                 sims = compute_clip_consistency(videos, audios, [category], net=clip_model)
                 ia, it = sims["ia_sim"].detach().cpu()[:, 1:], sims["it_sim"].detach().cpu()[:, 1:]                            # (b, f - 1)
@@ -163,7 +181,8 @@ def evaluate_generation_results(groundtruth_video_root: str, groundtruth_video_n
         groundtruth_avsync_scores=gt_scores if eval_relsync else None, generated_avsync_scores=gen_scores if eval_relsync else None,
         groundtruth_first_frame_ia_sims=gt_first_ia if eval_alignsync else None,
         generated_pred_frame_ia_sims=gen_pred_ia if eval_alignsync else None,
-        generated_video_names=gen_names if record_instance_metrics else None))
+        generated_video_names=gen_names if record_instance_metrics else None,
+        groundtruth_fvd_features=gt_fvd if eval_fvd else None, generated_fvd_features=gen_fvd if eval_fvd else None))
 
     os.makedirs(os.path.dirname(result_save_path) or ".", exist_ok=True)
     with open(result_save_path, "w") as f:

@@ -1432,13 +1432,77 @@ def pool3_hw_f32(x: torch.Tensor, mode: str, stride: int, pad: int, *, out: Opti
     return out
 
 
-def mean_rows_f32(x: torch.Tensor) -> torch.Tensor:
-    """[n, ..., c] -> [n, c]: mean over all positions of a sample"""
+def same_pad(size: int, k: int, s: int):
+    """TensorFlow "same" padding of one axis -> (front, back); the output is ceil(size / s) (pytorch_i3d.py:73-95)"""
+    total = max(k - (s if size % s == 0 else size % s), 0)
+    return total // 2, total - total // 2
+
+
+def conv3d_same_f32(x: torch.Tensor, w: torch.Tensor, taps, stride, *, out: Optional[torch.Tensor] = None,
+                    bias: Optional[torch.Tensor] = None, relu: bool = False, loader: int = 0, ldx: Optional[int] = None,
+                    ldy: Optional[int] = None) -> torch.Tensor:
+    """convnd_ld_f32 with "same" zero padding computed from the input size: x [n, t, h, w, cin] (a channel slice or dense) ->
+    [n, ceil(t / st), ceil(h / sh), ceil(w / sw), cout], into the channel slice `out` if given.  loader 0 picks; 1 / 2 / 3 force the
+    scalar / float4 / run loader (same bits; refused where illegal); see avsd_conv3d_same_f32"""
+    for t, name in ((w, "w"), (bias, "bias")):
+        if t is not None and (t.dtype != F32 or not t.is_cuda or not t.is_contiguous()):
+            raise ValueError(f"conv3d_same_f32: {name} must be a contiguous f32 device tensor")
+    if w.dim() != 2:
+        raise ValueError("conv3d_same_f32: w must be [cout, ldw]")
+    sx = _slice_ld(x, "conv3d_same_f32: x")
+    if ldx is not None and ldx > sx:
+        raise ValueError(f"conv3d_same_f32: ldx {ldx} is wider than the pixel stride {sx} of x")
+    ldx = sx if ldx is None else int(ldx)
+    n, ti, hi, wi, cin = x.shape
+    cout, ldw = w.shape
+    (kt, kh, kw), (st, sh, sw) = taps, stride
+    if min(st, sh, sw) < 1:
+        raise ValueError("conv3d_same_f32: strides must be positive")
+    to, ho, wo = -(-ti // st), -(-hi // sh), -(-wi // sw)
+    if bias is not None and bias.numel() != cout:
+        raise ValueError("conv3d_same_f32: bias must have cout entries")
+    if out is None:
+        out = torch.empty((n, to, ho, wo, cout), dtype=F32, device=x.device)
+    elif tuple(out.shape) != (n, to, ho, wo, cout):
+        raise ValueError(f"conv3d_same_f32: out {tuple(out.shape)} does not match {(n, to, ho, wo, cout)}")
+    sy = _slice_ld(out, "conv3d_same_f32: out")
+    if ldy is not None and ldy > sy:
+        raise ValueError(f"conv3d_same_f32: ldy {ldy} is wider than the pixel stride {sy} of out")
+    ldy = sy if ldy is None else int(ldy)
+    check(_lib.lib().avsd_conv3d_same_f32(_p(x), ldx, _p(w), _p(bias), _p(out), ldy, n, ti, hi, wi, cin, to, ho, wo, cout, kt, kh, kw, st, sh,
+                                          sw, ldw, int(relu), int(loader), _stream()), "avsd_conv3d_same_f32")
+    return out
+
+
+def maxpool3d_same_f32(x: torch.Tensor, window, stride, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """max pool with "same" padding on [n, t, h, w, c], windows 1 .. 3 and strides 1 .. 2 per axis; a padded position counts as 0.0;
+    x and `out` may be channel slices as in convnd_ld_f32; see avsd_maxpool3d_same_f32"""
+    ldx = _slice_ld(x, "maxpool3d_same_f32: x")
+    n, ti, hi, wi, c = x.shape
+    (kt, kh, kw), (st, sh, sw) = window, stride
+    if min(st, sh, sw) < 1:
+        raise ValueError("maxpool3d_same_f32: strides must be positive")
+    to, ho, wo = -(-ti // st), -(-hi // sh), -(-wi // sw)
+    if out is None:
+        out = torch.empty((n, to, ho, wo, c), dtype=F32, device=x.device)
+    elif tuple(out.shape) != (n, to, ho, wo, c):
+        raise ValueError(f"maxpool3d_same_f32: out {tuple(out.shape)} does not match {(n, to, ho, wo, c)}")
+    ldy = _slice_ld(out, "maxpool3d_same_f32: out")
+    check(_lib.lib().avsd_maxpool3d_same_f32(_p(x), ldx, _p(out), ldy, n, ti, hi, wi, c, to, ho, wo, kt, kh, kw, st, sh, sw, _stream()),
+          "avsd_maxpool3d_same_f32")
+    return out
+
+
+def mean_rows_f32(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[n, ..., c] -> [n, c]: mean over all positions of a sample, into the contiguous `out` [n, c] if given"""
     _req(x, F32, "x")
     if x.dim() < 2 or not x.is_contiguous():
         raise ValueError("mean_rows_f32: x must be contiguous [n, ..., c]")
     n, c = x.shape[0], x.shape[-1]
-    out = torch.empty((n, c), dtype=F32, device=x.device)
+    if out is None:
+        out = torch.empty((n, c), dtype=F32, device=x.device)
+    elif out.dtype != F32 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != (n, c):
+        raise ValueError(f"mean_rows_f32: out must be a contiguous f32 device tensor {(n, c)}")
     check(_lib.lib().avsd_mean_rows_f32(_p(x), _p(out), n, x.numel() // (n * c), c, _stream()), "avsd_mean_rows_f32")
     return out
 

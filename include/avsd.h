@@ -481,6 +481,26 @@ int avsd_convnd_ld_f32(const float* x, int ldx, const float* w, const float* bia
  * (dy, dx) order, divided by their number 4, 6 or 9 (F.avg_pool2d(count_include_pad=False), inception_v3.py:228). */
 int avsd_pool3_hw_f32(const float* x, int ldx, float* out, int ldy, int n_img, int hi, int wi, int c, int ho, int wo, int stride,
                       int pad, int avg, void* stream);
+/* avsd_convnd_ld_f32 with TensorFlow "same" zero padding (I3D, asva_amd/fvd.py; pytorch_i3d.py:73-98 of the reference), worked out
+ * inside from input size, window and stride, per axis: total = max(k - s, 0) if size % s == 0, else max(k - size % s, 0); total / 2
+ * (rounded down) in front, the rest behind; output ceil(size / s), which the caller passes as to, ho, wo (anything else is refused).
+ * The padding is asymmetric for even windows or strides > 1 (the 7 x 7 x 7 stride-2 stem on an even axis: 2 in front, 3 behind).  No
+ * residual.  For a stride-1 odd window the padding is (k - 1) / 2 on both sides and the result equals avsd_convnd_ld_f32 bit for bit.
+ * loader: 0 picks, 1 scalar (always legal), 2 float4 (cin % 32 == 0, ldx % 4 == 0, ldw % 4 == 0, x and w 16-byte aligned), 3 run
+ * (ldx == cin, ldw % 4 == 0, w 16-byte aligned: the kw * cin floats of one (dt, dh) row of the window are contiguous and are
+ * fetched four at a time with 4-byte-aligned wide loads, element by element at run boundaries, the w borders and the K tail — made
+ * for the stem, cin = 3, K = 1029); an illegal choice is refused.  0 takes 2 where legal, else 1: on the stem the run loader measured
+ * 2 % behind the scalar one (profiles/fvd.md), so it is never picked and stays for A/Bs.  Every loader gives the same bits: each
+ * output element is the k-ordered chain 0 .. K-1. */
+int avsd_conv3d_same_f32(const float* x, int ldx, const float* w, const float* bias, float* out, int ldy, int n, int ti, int hi, int wi,
+                         int cin, int to, int ho, int wo, int cout, int kt, int kh, int kw, int st, int sh, int sw, int ldw, int relu,
+                         int loader, void* stream);
+/* Max pool with "same" padding on [n][ti][hi][wi][c] -> [n][to][ho][wo][c], pixels ldx / ldy elements apart (channel slices; c, ldx,
+ * ldy multiples of 4, pointers 16-byte aligned).  Windows 1 .. 3 and strides 1 .. 2 per axis; to, ho, wo must be ceil(size / stride).
+ * A padded position takes part in the maximum as 0.0f: the reference pads with F.pad and then pools without padding
+ * (pytorch_i3d.py:17-36), unlike avsd_pool3_hw_f32 and avsd_maxpool_hw_f32.  Exact. */
+int avsd_maxpool3d_same_f32(const float* x, int ldx, float* out, int ldy, int n, int ti, int hi, int wi, int c, int to, int ho, int wo,
+                            int kt, int kh, int kw, int st, int sh, int sw, void* stream);
 /* nn.MaxPool3d((1,3,3), stride (1,2,2), padding (0,1,1)) (video.py:62) on [n_img][hi][wi][c] -> [n_img][ho][wo][c]; padded
  * positions do not take part.  c a multiple of 4. */
 int avsd_maxpool_hw_f32(const float* x, float* out, int n_img, int hi, int wi, int c, int ho, int wo, void* stream);
