@@ -12,10 +12,17 @@ Kaldi algorithm with torchaudio's defaults (povey-free hanning window, pre-empha
 snip_edges, power spectrum, 20 Hz .. Nyquist mel triangles on the 1127 ln(1 + f / 700) scale, log floor at float32
 eps) — parity unpinned (oracle/audio_ref.py says the same).  The whole-clip mean subtraction of waveform2melspec is
 dropped: the per-frame DC removal that follows cancels any constant offset exactly.
+
+`resample` is the sample-rate converter in front of it, host side of `avsd_resample_sinc_f32`: the reference brings every
+real input to 16 kHz with `torchaudio.functional.resample` (avgen/data/utils.py:259,404, compute_avsync.py:141,157).
+`resample_taps` restates torchaudio's published windowed-sinc filter bank (`_get_sinc_resample_kernel`) in float64 and is
+the only place the filter is defined; torchaudio is not in this image either, so this too is parity unpinned: the filter
+is checked against its definition and against closed-form answers (tests/test_resample_cpu.py), not against torchaudio.
 """
 from __future__ import annotations
 
-from typing import List, Union
+import math
+from typing import List, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -71,6 +78,110 @@ class _Tables:
 
 
 _TABLES = _Tables()
+
+
+# ---- sample-rate conversion ------------------------------------------------------------------------------------------
+RESAMPLING_METHODS = ("sinc_interp_hann", "sinc_interp_kaiser")
+KAISER_BETA = 14.769656459379492              # torchaudio's default for sinc_interp_kaiser
+MAX_TAPS = 1 << 24                            # floats in a filter bank; avsd_resample_sinc_f32 refuses more
+
+
+def _int_rate(v, name: str) -> int:
+    if isinstance(v, bool) or int(v) != v or int(v) <= 0:
+        raise ValueError(f"resample: {name} must be a positive integer sample rate, got {v!r}")
+    return int(v)
+
+
+def _resample_geometry(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method) -> Tuple[int, int, int, float]:
+    """-> (orig, new, width, base); every argument error of `resample` / `resample_taps` is raised here, on the host."""
+    if resampling_method not in RESAMPLING_METHODS:
+        raise ValueError(f"resample: unknown resampling_method {resampling_method!r}; one of {RESAMPLING_METHODS}")
+    orig_freq, new_freq = _int_rate(orig_freq, "orig_freq"), _int_rate(new_freq, "new_freq")
+    if lowpass_filter_width <= 0 or not rolloff > 0.0:
+        raise ValueError("resample: lowpass_filter_width and rolloff must be positive")
+    g = math.gcd(orig_freq, new_freq)
+    orig, new = orig_freq // g, new_freq // g
+    base = min(orig, new) * float(rolloff)
+    width = int(math.ceil(lowpass_filter_width * orig / base))
+    L = 2 * width + orig
+    if new * L > MAX_TAPS:
+        raise ValueError(f"resample: {orig_freq} -> {new_freq} Hz reduces to {orig} : {new}, a filter bank of {new} x {L} taps "
+                         f"(more than {MAX_TAPS} floats); rates with a larger common divisor are needed")
+    return orig, new, width, base
+
+
+def resample_taps(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99,
+                  resampling_method: str = "sinc_interp_hann", beta: Optional[float] = None) -> Tuple[np.ndarray, int, int, int]:
+    """-> (taps f32 [new][L], width, orig, new): torchaudio's polyphase windowed-sinc filter bank, L = 2 * width + orig, with
+    orig : new the two rates divided by their gcd.  Output sample q * new + p is sum_k taps[p][k] * x[q * orig + k - width]
+    (x zero outside the clip).  Computed in float64, cast to f32 at the end."""
+    orig, new, width, base = _resample_geometry(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method)
+    k = np.arange(-width, width + orig, dtype=np.float64)[None, :] / orig
+    p = np.arange(new, dtype=np.float64)[:, None] / new
+    t = np.clip((k - p) * base, -lowpass_filter_width, lowpass_filter_width)
+    if resampling_method == "sinc_interp_hann":
+        window = np.cos(t * math.pi / lowpass_filter_width / 2.0) ** 2
+    else:
+        b = KAISER_BETA if beta is None else float(beta)
+        window = np.i0(b * np.sqrt(np.maximum(1.0 - (t / lowpass_filter_width) ** 2, 0.0))) / np.i0(b)
+    t = t * math.pi
+    sinc = np.where(t == 0.0, 1.0, np.sin(t) / np.where(t == 0.0, 1.0, t))
+    taps = sinc * window * (base / orig)
+    return np.ascontiguousarray(taps.astype(np.float32)), width, orig, new
+
+
+def resample_length(n_samples: int, orig_freq: int, new_freq: int) -> int:
+    """samples `resample` returns for n_samples: ceil(new_freq * n_samples / orig_freq), in integers"""
+    orig_freq, new_freq = _int_rate(orig_freq, "orig_freq"), _int_rate(new_freq, "new_freq")
+    g = math.gcd(orig_freq, new_freq)
+    return (new_freq // g * int(n_samples) + orig_freq // g - 1) // (orig_freq // g)
+
+
+class _ResampleTaps:
+    """Filter banks uploaded once per (device, rates, filter parameters), as _Tables."""
+
+    def __init__(self):
+        self._cache = {}
+
+    def get(self, device, orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method, beta):
+        g = math.gcd(int(orig_freq), int(new_freq))
+        key = (str(device), int(orig_freq) // g, int(new_freq) // g, lowpass_filter_width, float(rolloff), resampling_method,
+               None if beta is None else float(beta))
+        t = self._cache.get(key)
+        if t is None:
+            taps, width, orig, new = resample_taps(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method, beta)
+            t = (torch.from_numpy(taps).to(device), width, orig, new)
+            self._cache[key] = t
+        return t
+
+
+_RESAMPLE_TAPS = _ResampleTaps()
+
+
+def resample(waveform: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99,
+             resampling_method: str = "sinc_interp_hann", beta: Optional[float] = None, device=None) -> torch.Tensor:
+    """`torchaudio.functional.resample` on the device: (..., time) -> (..., ceil(new_freq * time / orig_freq)).  Equal rates
+    return `waveform` itself, as torchaudio does.  A host tensor is uploaded to `device` (default: cuda); the result stays on
+    the device it was computed on, in the dtype of the input (the arithmetic is f32)."""
+    _resample_geometry(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method)
+    if int(orig_freq) == int(new_freq):
+        return waveform
+    if not isinstance(waveform, torch.Tensor) or not waveform.is_floating_point() or waveform.dim() < 1 or waveform.numel() == 0:
+        raise ValueError("resample: waveform must be a non-empty floating-point tensor (..., time)")
+    if device is None:
+        device = waveform.device if waveform.is_cuda else torch.device("cuda")
+    device = torch.device(device)
+    if device.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError(f"resample: the resampler runs on the GPU only (asked for {device}, "
+                           f"torch.cuda.is_available() = {torch.cuda.is_available()}); there is no host path")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    taps, width, orig, new = _RESAMPLE_TAPS.get(device, orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method, beta)
+    lead = waveform.shape[:-1]
+    rows = waveform.reshape(-1, waveform.shape[-1]).to(device=device, dtype=torch.float32).contiguous()
+    with torch.cuda.device(device):
+        out = ops.resample_sinc_f32(rows, taps, orig, new, width)
+    return out.view(*lead, out.shape[-1]).to(waveform.dtype)
 
 
 def waveform_to_melspectrogram(waveform: Union[np.ndarray, torch.Tensor], num_mel_bins: int = 128, target_length: int = 204,

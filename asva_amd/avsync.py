@@ -480,10 +480,12 @@ def compute_sync_metrics_on_av(audio_waveform: torch.Tensor, audio_sr: int, vide
                                ref_audio_waveform: Optional[torch.Tensor] = None, ref_audio_sr: Optional[int] = None,
                                ref_video: Optional[torch.Tensor] = None, metric: str = "alignsync", device=torch.device("cuda"),
                                dtype: torch.dtype = torch.float32, net: Optional[AVSyncClassifier] = None, clip_net=None):
-    """compute_avsync.py:105-end: waveform (c, samples) at 16 kHz, video (3, 12, h, w) in [0, 1].  `net` defaults to
+    """compute_avsync.py:105-end: waveform (c, samples) at 16 kHz - or, under data_utils.set_resampler("device"), at any rate,
+    resampled on the device as compute_avsync.py:141,157 do with torchaudio - video (3, 12, h, w) in [0, 1].  `net` defaults to
     load_avsync_model() (loaded once per process).  metric="alignsync" needs `ref_video` and `clip_net`, the ImageBind towers of
     asva_amd.imagebind_eval.load_clip_model(path): their checkpoint is not fetched here."""
-    from .audio_features import waveform_to_melspectrogram
+    from .audio_features import resample, waveform_to_melspectrogram
+    from .data_utils import get_resampler
 
     if metric not in ("alignsync", "relsync", "avsync_score"):
         raise ValueError(f"unknown metric {metric!r}")
@@ -500,8 +502,13 @@ def compute_sync_metrics_on_av(audio_waveform: torch.Tensor, audio_sr: int, vide
         raise ValueError("To compute relsync, either ref_audio_waveform or ref_video is needed as reference")
     ref_audio_sr = audio_sr if ref_audio_sr is None else ref_audio_sr
     for sr in (audio_sr,) + ((ref_audio_sr,) if ref_audio_waveform is not None else ()):
-        if sr != 16000:
-            raise ValueError(f"audio at {sr} Hz: resample to 16000 Hz first (there is no resampler here)")
+        if sr != 16000 and get_resampler() != "device":
+            raise ValueError(f"audio at {sr} Hz: resample to 16000 Hz first, or let this function do it on the device with "
+                             'asva_amd.data_utils.set_resampler("device") / AVSD_RESAMPLER=device')
+    if audio_sr != 16000:
+        audio_waveform = resample(audio_waveform, audio_sr, 16000, device=device)
+    if ref_audio_waveform is not None and ref_audio_sr != 16000:
+        ref_audio_waveform = resample(ref_audio_waveform, ref_audio_sr, 16000, device=device)
     if net is None:
         net = _NETS.get(str(device))
         if net is None:

@@ -85,6 +85,8 @@ const Entry kEntries[] = {
     // ImageBind evaluation towers (csrc/imagebind_eval.hip)
     AVSD_PLAN_ENTRY(avsd_attention_f32),    AVSD_PLAN_ENTRY(avsd_gelu_f32),              AVSD_PLAN_ENTRY(avsd_vit_tokens_f32),
     AVSD_PLAN_ENTRY(avsd_cosine_rows_f32),   AVSD_PLAN_ENTRY(avsd_normalize_rows_f32),
+    // sample-rate conversion (csrc/audio.hip)
+    AVSD_PLAN_ENTRY(avsd_resample_sinc_f32),
 };
 
 struct Reloc {

@@ -6,9 +6,13 @@ names, arguments, return shapes and value ranges.
 Backends.  The reference decodes with torchvision.io.VideoReader / torchaudio / PIL.  This image has PIL, scipy and
 numpy only, so
   * images: PIL (as the reference);
-  * audio files: torchaudio when importable, else `.wav` through scipy.io.wavfile; resampling through
-    torchaudio.functional.resample when importable, else scipy.signal.resample_poly (both are polyphase windowed-sinc
-    resamplers; their filters differ, so waveforms agree to ~1e-3, not bit for bit);
+  * audio files: torchaudio when importable, else `.wav` through scipy.io.wavfile;
+  * resampling to 16 kHz: chosen by `set_resampler` / $AVSD_RESAMPLER.  "host" (the default): torchaudio.functional.resample
+    when importable, else scipy.signal.resample_poly.  Both are polyphase windowed-sinc resamplers, but their filters differ
+    (torchaudio: Hann-windowed sinc, 6 zero crossings, cutoff at 0.99 Nyquist; scipy: a Kaiser(5) FIR with a wider transition
+    band), and on broadband input the two waveforms differ by about 7e-2 rel-L2 (white noise, 44.1 / 48 / 22.05 -> 16 kHz),
+    not 1e-3.  "device": `asva_amd.audio_features.resample`, torchaudio's filter as a HIP kernel; the loaders still return host
+    waveforms;
   * video files: torchvision's VideoReader when importable; additionally a pre-decoded clip container
     (`.npz` with `frames` uint8 (T, H, W, 3), `fps`, optional `audio` f32 (C, T) + `audio_sr`) that needs no codec —
     what the synthetic dataset driver test and offline-decoded datasets use.  A real `.mp4` without torchvision
@@ -92,9 +96,34 @@ def load_image(image_path: str, image_size=(256, 256)) -> torch.Tensor:
 
 
 # ---- audio ------------------------------------------------------------------------------------------------------------
+_RESAMPLERS = ("host", "device")
+_resampler = "host"
+
+
+def set_resampler(mode: str) -> None:
+    """Where `_resample` (every loader here) and `avsync.compute_sync_metrics_on_av` convert sample rates.  "host": torchaudio
+    if importable, else scipy.signal.resample_poly - the default.  "device": `audio_features.resample` (torchaudio's filter,
+    avsd_resample_sinc_f32); needs a GPU.  Read once from $AVSD_RESAMPLER at import."""
+    global _resampler
+    if mode not in _RESAMPLERS:
+        raise ValueError(f"set_resampler: unknown mode {mode!r}; one of {_RESAMPLERS}")
+    if mode == "device" and not torch.cuda.is_available():
+        raise RuntimeError('set_resampler("device"): no GPU is available (torch.cuda.is_available() is False) and the device '
+                           'resampler has no host path; use "host"')
+    _resampler = mode
+
+
+def get_resampler() -> str:
+    return _resampler
+
+
 def _resample(audio: torch.Tensor, orig: int, new: int = 16000) -> torch.Tensor:
     if orig == new:
         return audio
+    if _resampler == "device":
+        from .audio_features import resample
+
+        return resample(audio, orig, new).to(audio.device)       # host waveforms in, host waveforms out
     try:
         import torchaudio  # type: ignore
 
@@ -106,6 +135,10 @@ def _resample(audio: torch.Tensor, orig: int, new: int = 16000) -> torch.Tensor:
 
         g = gcd(int(orig), int(new))
         return torch.from_numpy(resample_poly(audio.numpy().astype(np.float64), new // g, orig // g, axis=1).astype(np.float32))
+
+
+if os.environ.get("AVSD_RESAMPLER"):
+    set_resampler(os.environ["AVSD_RESAMPLER"])
 
 
 def _load_audio_file(path: str) -> Tuple[torch.Tensor, int]:

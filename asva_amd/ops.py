@@ -1288,6 +1288,41 @@ def kaldi_fbank(wave: torch.Tensor, window: torch.Tensor, mel_fb: torch.Tensor, 
     return out
 
 
+# q (groups of `new` outputs that share one input window) per workgroup of avsd_resample_sinc_f32: 256 where that window fits
+# 64 KiB of LDS, else 64 (csrc/audio.hip).  Tile boundaries sit at multiples of these times `orig` input samples.
+RESAMPLE_QT = (64, 256)
+
+
+def resample_sinc_f32(wave: torch.Tensor, taps: torch.Tensor, orig: int, new: int, width: int,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """wave (n_wav, n_in) f32 -> (n_wav, ceil(new * n_in / orig)) f32 through the filter bank taps [new][2 * width + orig]
+    (audio_features.resample_taps); see avsd_resample_sinc_f32.  Rows may be strided (views of a wider buffer); `out`, if
+    given, is such a view to write into."""
+    for name, t in (("wave", wave), ("taps", taps)) + ((("out", out),) if out is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"resample_sinc_f32: {name} must be a device tensor (libavsd_hip.so has no host path)")
+        if t.dtype != F32:
+            raise ValueError(f"resample_sinc_f32: {name} must be float32, got {t.dtype}")
+    orig, new, width = int(orig), int(new), int(width)
+    if orig <= 0 or new <= 0 or width <= 0:
+        raise ValueError(f"resample_sinc_f32: orig, new, width must be positive, got {orig}, {new}, {width}")
+    if wave.dim() != 2 or wave.shape[0] == 0 or wave.shape[1] == 0 or wave.stride(1) != 1:
+        raise ValueError(f"resample_sinc_f32: wave must be a non-empty (n_wav, n_in) with unit inner stride, got {tuple(wave.shape)}")
+    if tuple(taps.shape) != (new, 2 * width + orig) or not taps.is_contiguous():
+        raise ValueError(f"resample_sinc_f32: taps must be contiguous [{new}][{2 * width + orig}], got {tuple(taps.shape)}")
+    n_wav, n_in = wave.shape
+    n_out = (new * n_in + orig - 1) // orig
+    if out is None:
+        out = torch.empty((n_wav, n_out), dtype=F32, device=wave.device)
+    elif tuple(out.shape) != (n_wav, n_out) or out.stride(1) != 1 or out.device != wave.device:
+        raise ValueError(f"resample_sinc_f32: out must be ({n_wav}, {n_out}) with unit inner stride on {wave.device}")
+    check(_lib.lib().avsd_resample_sinc_f32(_p(wave), n_wav, n_in, wave.stride(0) if n_wav > 1 else max(wave.stride(0), n_in),
+                                            _p(taps), orig, new, width, _p(out), n_out,
+                                            out.stride(0) if n_wav > 1 else max(out.stride(0), n_out), _stream()),
+          "avsd_resample_sinc_f32")
+    return out
+
+
 def patchify(x: torch.Tensor, kh: int, kw: int, stride: int) -> torch.Tensor:
     """(B, C, H, W) f32 -> bf16 rows [B*ph*pw, C*kh*kw]."""
     _req(x, F32, "x")

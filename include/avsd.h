@@ -386,6 +386,15 @@ int avsd_vae_postprocess_u8(const void* src, int ld, void* dst_u8, int N, int HW
 int avsd_kaldi_fbank(const float* wave, int batch, int n_samples, int64_t wave_stride, const float* window,
                      const float* mel_fb, int win, int shift, int nfft, int n_mel, float preemph, int remove_dc,
                      float* out, int t_out, float mean, float std, void* stream);
+/* Polyphase windowed-sinc sample-rate conversion (torchaudio.functional.resample: avgen/data/utils.py:259,404,
+ * compute_avsync.py:141,157), f32 in both builds.  `orig` : `new_` are the two rates divided by their gcd, taps
+ * [new_][L] f32 with L = 2 * width + orig is the filter bank (host-built, asva_amd/audio_features.py:resample_taps):
+ *   out[w][q * new_ + p] = sum_{k < L} taps[p][k] * xpad(w, q * orig + k - width)      for q * new_ + p < n_out,
+ * xpad = x inside [0, n_in) and 0 outside (the kernel pads; it never reads outside a row).  x [n_wav][x_stride],
+ * out [n_wav][out_stride]; n_out must be ceil(new_ * n_in / orig) and new_ * L at most 2^24.  Every output is one
+ * k-ascending f32 fma chain: bits do not depend on n_wav or on the build. */
+int avsd_resample_sinc_f32(const float* x, int n_wav, int n_in, int64_t x_stride, const float* taps, int orig, int new_,
+                           int width, float* out, int n_out, int64_t out_stride, void* stream);
 /* im2col of non-padded strided patches: src (B, C, H, W) f32 -> dst bf16 [B*ph*pw][C*kh*kw] (c-major, then kh, kw:
  * the order of a flattened nn.Conv2d weight).  Front of ImageBind's audio stem Conv2d(1, 768, 16, stride 10). */
 int avsd_patchify(const float* src, void* dst, int B, int C, int H, int W, int kh, int kw, int stride, void* stream);
