@@ -79,6 +79,8 @@ SIGNATURES = {
     "avsd_gemm_conv3r2d_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "avsd_cross_attention_block_supported": (c_int, [c_int, c_int, c_int]),
     "avsd_sizeof_xattn_desc": (c_int, []),
+    "avsd_qproj_attention": (c_int, [C.POINTER(XAttnDesc), c_void_p]),
+    "avsd_qproj_attention_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "avsd_linear_small_m": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "avsd_groupnorm_stats": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "avsd_groupnorm_apply": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float,

@@ -1126,6 +1126,59 @@ def cross_attention_block(h: torch.Tensor, stats: torch.Tensor, wq: torch.Tensor
     return out
 
 
+def qproj_attention_supported(C: int, heads: int, lk_pad: int, M: int, L: int, q_per_kv: int) -> bool:
+    """LayerNorm-folded Q projection + cross-attention as one launch (avsd_qproj_attention): the wider levels the fused block is not built for"""
+    return (not P.SPLIT and L > 0 and q_per_kv > 0 and M % (L * q_per_kv) == 0
+            and bool(_lib.lib().avsd_qproj_attention_supported(C, heads, lk_pad, L * q_per_kv)))
+
+
+def qproj_attention(h: torch.Tensor, stats: torch.Tensor, wq: torch.Tensor, q_colsum: torch.Tensor, q_bias: torch.Tensor,
+                    k: torch.Tensor, vt: torch.Tensor, lk: int, *, heads: int, L: int, q_per_kv: int, eps: float = 1e-5,
+                    scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = softmax((LN(h) Wq^T) K^T scale) V in one launch; see avsd_qproj_attention (include/avsd.h).  Operands as
+    cross_attention_block: k [nkv, lk_pad, C], vt [nkv, C, lk_pad] are the cached, padded K / V^T."""
+    if P.SPLIT:
+        raise ValueError("qproj_attention: not built for split precision (use the separate kernels)")
+    _req(h, P.ACT, "h")
+    _req(wq, P.ACT, "wq")
+    _req(k, P.ACT, "k")
+    _req(vt, P.ACT, "vt")
+    _req(stats, F32, "stats")
+    _req(q_colsum, F32, "q_colsum")
+    _req(q_bias, F32, "q_bias")
+    M, Cc = h.shape
+    if k.dim() != 3 or not k.is_contiguous() or not vt.is_contiguous() or vt.shape != (k.shape[0], Cc, k.shape[1]) or k.shape[2] != Cc:
+        raise ValueError("qproj_attention: k must be contiguous [nkv, lk_pad, C] and vt [nkv, C, lk_pad]")
+    lk_pad = k.shape[1]
+    if not stats.is_contiguous() or stats.shape != (M, Cc // 32, 2):
+        raise ValueError("qproj_attention: stats must be contiguous f32 [M, C/32, 2]")
+    if wq.shape != (Cc, Cc) or q_colsum.numel() != Cc or q_bias.numel() != Cc or not q_colsum.is_contiguous() or not q_bias.is_contiguous():
+        raise ValueError("qproj_attention: wq [C, C] with q_colsum [C] and q_bias [C] expected")
+    if L <= 0 or q_per_kv <= 0 or M % L or (M // L) % q_per_kv or (M // L) // q_per_kv > k.shape[0]:
+        raise ValueError("qproj_attention: K/V blocks do not cover the query batches")
+    if out is None:
+        out = torch.empty((M, Cc), dtype=P.ACT, device=h.device)
+    _req(out, P.ACT, "out")
+    if out.shape != (M, Cc):
+        raise ValueError("qproj_attention: out must be [M, C]")
+    d = XAttnDesc()
+    d.h, d.ldh = _p(h), _ld(h)
+    d.M, d.C, d.heads, d.L = M, Cc, heads, L
+    d.ln_stats, d.ln_eps = _p(stats), float(eps)
+    d.scale = float(scale) if scale is not None else float(Cc // heads) ** -0.5
+    d.wq, d.ldwq, d.q_colsum, d.q_bias = _p(wq), _ld(wq), _p(q_colsum), _p(q_bias)
+    d.k, d.vt, d.lk, d.lk_pad, d.q_per_kv = _p(k), _p(vt), lk, lk_pad, q_per_kv
+    d.out, d.ldo = _p(out), _ld(out)
+    ev = _TIMER.start() if _TIMER is not None else None
+    check(_lib.lib().avsd_qproj_attention(C.byref(d), _stream()), "avsd_qproj_attention")
+    if ev is not None:
+        dc = XAttnDesc.from_buffer_copy(d)
+        _TIMER.add_replay("qproj_attention", lambda dc=dc: check(_lib.lib().avsd_qproj_attention(C.byref(dc), _stream()), "avsd_qproj_attention"),
+                          (h, stats, wq, q_colsum, q_bias, k, vt, out))
+        _TIMER.stop(ev, "qproj_attention", 2.0 * M * Cc * Cc + 4.0 * M * lk * Cc, _nbytes(h, out) + 2.0 * Cc * Cc)
+    return out
+
+
 def temporal_attention(qkv: torch.Tensor, *, b: int, frames: int, hw: int, heads: int,
                        scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _req(qkv, P.ACT, "qkv")

@@ -46,6 +46,9 @@ _F32_RES = os.environ.get("AVSD_F32_RESIDUAL", "0") != "0"
 # Per model: `unet.fp8_attention = True` (optionally `unet.fp8_scales = (q, k, v)` per-tensor scales, default 1.0).
 _ATTN_FP8 = os.environ.get("AVSD_ATTN_FP8", "0") != "0"
 _FUSE_XATTN = True
+# below 32 x 32 (C = 640 / 1280), where the one-launch block is not built: Q projection + cross-attention as one launch
+# (avsd_qproj_attention), the output projection stays a GEMM.  AVSD_FUSE_QATTN=0 runs the three launches, for A/B runs.
+_FUSE_QATTN = os.environ.get("AVSD_FUSE_QATTN", "1") != "0"
 # the GEGLU projection re-folds the K / 32 LayerNorm partials of its rows in each of its 20-80 column tiles (+8-10 us per launch): fold
 # them once in a tiny launch (avsd_ln_fold) and hand it one pair per row
 _LN_PREFOLD = True
@@ -1100,6 +1103,12 @@ def _transformer(st, x: _Act, p, hw, heads, split: int = 1, rest=False) -> _Act:
             out = ops.cross_attention_block(h.lo, s_in, a.wq_ln, a.sq_ln, a.bq_ln, xa.k, xa.vt, xa.lk, a.wo, a.bo, res=h.res,
                                             heads=heads, L=L, q_per_kv=xa.q_per_kv, eps=eps, rowstats=s_out, master=m, stats_pos=stats_pos)
             return _Act(out, m)
+        qa_ok = getattr(ops, "qproj_attention_supported", None)
+        if (_FUSE_QATTN and fused and st.fp8 is None and xa is not None and qa_ok is not None
+                and qa_ok(C, heads, xa.k.shape[1], M, L, xa.q_per_kv)):
+            o = ops.qproj_attention(h.lo, stats[si], a.wq_ln, a.sq_ln, a.bq_ln, xa.k, xa.vt, xa.lk, heads=heads, L=L,
+                                    q_per_kv=xa.q_per_kv, eps=eps)
+            return stream(o, a.wo, a.bo, h, want_stats=want_stats, stats_pos=stats_pos)
         return stream(unfused(), a.wo, a.bo, h, want_stats=want_stats, stats_pos=stats_pos)
 
     def proj(h, norm, wl, bl, sl, w_plain):

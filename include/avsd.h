@@ -241,6 +241,15 @@ int avsd_cross_attention_block_supported(int C, int heads, int lk_pad);
 int avsd_cross_attention_block(const avsd_xattn_desc* desc_host, void* stream);
 int avsd_sizeof_xattn_desc(void);
 
+/* Stages 1-2 of the block above for the wider levels, split by head: one launch for
+ *     out[M][ldo] = softmax( (LayerNorm(h) Wq^T) K^T * scale ) V        (16-bit)
+ * in place of the LayerNorm-folded Q projection and the attention launch; the output projection stays a GEMM.  Takes the same
+ * descriptor: wo, o_bias, res, rowstats, out_master and stats_pos must be null.  Built for C = 640 / 1280 with 8 heads and
+ * lk_pad in {32, 64, 96}, where a K/V block serves rows_per_kv_block = L * q_per_kv rows that are whole 64-row tiles:
+ * avsd_qproj_attention_supported() tells; anything else is AVSD_EINVAL and runs as the separate kernels. */
+int avsd_qproj_attention_supported(int C, int heads, int lk_pad, int rows_per_kv_block);
+int avsd_qproj_attention(const avsd_xattn_desc* desc_host, void* stream);
+
 /* out[M, N] (f32) = act_out( act_in(x[M, K] f32) . W[N, K]^T + bias ), M <= 16.
  * act: 0 none, 1 SiLU.  Time-embedding MLP and the per-ResBlock time_emb_proj
  * (audio_cond_unet_3d_condition.py:673-680, ff_spatio_temp_resnet_3d.py:170), and the
