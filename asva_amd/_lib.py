@@ -105,6 +105,9 @@ SIGNATURES = {
                                  c_int, c_void_p, c_void_p, c_float, c_float, c_int, c_int, c_int, c_int, c_void_p]),
     "avsd_guided_multistep": (c_int, [c_void_p, c_int, c_float, c_float, c_void_p, c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float),
                                       c_int, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int, c_int, c_int, c_int, c_void_p]),
+    "avsd_guided_unipc": (c_int, [c_void_p, c_int, c_float, c_float, c_void_p, c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                  C.POINTER(C.c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float,
+                                  c_float, c_float, c_int, c_int, c_int, c_int, c_void_p]),
     "avsd_vae_postprocess":(c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     "avsd_vae_postprocess_u8": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     "avsd_kaldi_fbank": (c_int, [c_void_p, c_int, c_int, C.c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int,

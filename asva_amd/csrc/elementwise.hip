@@ -175,6 +175,51 @@ __global__ void guided_multistep_kernel(const MultistepArgs a) {
   }
 }
 
+struct UniPCArgs {
+  const float* noise_pred; float* hist; const float* x_in; float* x_out; float* x_last;
+  int n_branch, store_slot, n_hist, use_corrector;
+  int hist_idx[4];
+  float wc[4], wp[4];
+  float g, g2, s_x, s_e, cc_last, cc_cur, cp_x, cp_cur;
+  int B, C, F, HW;
+};
+
+// UniPC step: the corrector of the sample the UNet just saw, then the predictor for the next sigma (include/avsd.h).  Unlike the
+// two kernels above, every history slot is read BEFORE this step's data prediction is stored, so the store may take the oldest one.
+__global__ void guided_unipc_kernel(const UniPCArgs a) {
+  const int64_t per = (int64_t)a.B * a.C * a.F * a.HW;
+  const int64_t fhw = (int64_t)a.F * a.HW;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < per; i += (int64_t)gridDim.x * blockDim.x) {
+    float eps = a.noise_pred[i];
+    if (a.n_branch >= 2) {      // the guidance rule of guided_step_kernel
+      const float e1 = a.noise_pred[per + i];
+      float gsum = eps + a.g * (e1 - eps);
+      if (a.n_branch == 3) gsum = gsum + a.g2 * (a.noise_pred[2 * per + i] - e1);
+      eps = gsum;
+    }
+    const float xin = a.x_in[i];
+    const float d = fmaf(a.s_x, xin, a.s_e * eps);
+    float h[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) h[k] = (k < a.n_hist) ? a.hist[(int64_t)a.hist_idx[k] * per + i] : 0.f;
+    float xc = xin;
+    if (a.use_corrector) {
+      xc = fmaf(a.cc_cur, d, a.cc_last * a.x_last[i]);
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k < a.n_hist) xc = fmaf(a.wc[k], h[k], xc);
+    }
+    float acc = fmaf(a.cp_cur, d, a.cp_x * xc);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (k < a.n_hist) acc = fmaf(a.wp[k], h[k], acc);
+    const bool first = (i % fhw) / a.HW == 0;
+    if (a.store_slot >= 0) a.hist[(int64_t)a.store_slot * per + i] = d;
+    a.x_last[i] = first ? xin : xc;
+    a.x_out[i] = first ? xin : acc;
+  }
+}
+
 __global__ void vae_postprocess_kernel(const h16_t* src, int ld, int64_t src_lo, float* dst, int N, int HW) {
   const int64_t n = (int64_t)N * 3 * HW;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -346,6 +391,34 @@ extern "C" int avsd_guided_multistep(const float* noise_pred, int n_branch, floa
   const int64_t n = (int64_t)B * C * F * HW;
   hipLaunchKernelGGL(guided_multistep_kernel, dim3(grid_for(n, 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
   AVSD_CHECK_LAUNCH("guided_multistep launch");
+  return AVSD_OK;
+}
+
+extern "C" int avsd_guided_unipc(const float* noise_pred, int n_branch, float g, float g2, float* hist, int store_slot,
+                                 const int32_t* hist_idx, const float* wc, const float* wp, int n_hist, const float* x_in,
+                                 float* x_out, float* x_last, int use_corrector, float s_x, float s_e, float cc_last,
+                                 float cc_cur, float cp_x, float cp_cur, int B, int C, int F, int HW, void* stream) {
+  AVSD_REQUIRE(noise_pred && x_in && x_out && x_last, "guided_unipc: null pointer");
+  AVSD_REQUIRE(n_branch >= 1 && n_branch <= 3, "guided_unipc: n_branch must be 1, 2 or 3");
+  AVSD_REQUIRE(n_hist >= 0 && n_hist <= 4, "guided_unipc: n_hist must be in [0, 4]");
+  AVSD_REQUIRE((n_hist == 0 && store_slot < 0) || hist, "guided_unipc: history requested without hist");
+  AVSD_REQUIRE(n_hist == 0 || (hist_idx && wc && wp), "guided_unipc: null history tables");
+  AVSD_REQUIRE(x_last != x_in && x_last != x_out, "guided_unipc: x_last must not alias x_in or x_out");
+  AVSD_REQUIRE(B > 0 && C > 0 && F > 0 && HW > 0, "guided_unipc: bad shape");
+  for (int k = 0; k < n_hist; ++k) AVSD_REQUIRE(hist_idx[k] >= 0, "guided_unipc: negative history slot");
+  UniPCArgs a;
+  a.noise_pred = noise_pred; a.hist = hist; a.x_in = x_in; a.x_out = x_out; a.x_last = x_last;
+  a.n_branch = n_branch; a.store_slot = store_slot; a.n_hist = n_hist; a.use_corrector = use_corrector != 0;
+  for (int k = 0; k < 4; ++k) {
+    a.hist_idx[k] = k < n_hist ? hist_idx[k] : 0;
+    a.wc[k] = k < n_hist ? wc[k] : 0.f;
+    a.wp[k] = k < n_hist ? wp[k] : 0.f;
+  }
+  a.g = g; a.g2 = g2; a.s_x = s_x; a.s_e = s_e; a.cc_last = cc_last; a.cc_cur = cc_cur; a.cp_x = cp_x; a.cp_cur = cp_cur;
+  a.B = B; a.C = C; a.F = F; a.HW = HW;
+  const int64_t n = (int64_t)B * C * F * HW;
+  hipLaunchKernelGGL(guided_unipc_kernel, dim3(grid_for(n, 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  AVSD_CHECK_LAUNCH("guided_unipc launch");
   return AVSD_OK;
 }
 

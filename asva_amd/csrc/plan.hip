@@ -72,7 +72,7 @@ const Entry kEntries[] = {
     AVSD_PLAN_ENTRY(avsd_ncfhw_to_rows_x2), AVSD_PLAN_ENTRY(avsd_split_f32),             AVSD_PLAN_ENTRY(avsd_vae_postprocess_x2),
     AVSD_PLAN_ENTRY(avsd_vae_postprocess_u8_x2), AVSD_PLAN_ENTRY(avsd_softmax_rows_x2),
     AVSD_PLAN_ENTRY(avsd_groupnorm_fused),  AVSD_PLAN_ENTRY(avsd_groupnorm_fused_x2),
-    AVSD_PLAN_ENTRY(avsd_ln_fold),          AVSD_PLAN_ENTRY(avsd_guided_multistep),
+    AVSD_PLAN_ENTRY(avsd_ln_fold),          AVSD_PLAN_ENTRY(avsd_guided_multistep),      AVSD_PLAN_ENTRY(avsd_guided_unipc),
     // AVSync scorer (csrc/avsync.hip)
     AVSD_PLAN_ENTRY(avsd_convnd_f32),       AVSD_PLAN_ENTRY(avsd_maxpool_hw_f32),        AVSD_PLAN_ENTRY(avsd_mean_rows_f32),
     AVSD_PLAN_ENTRY(avsd_resize_aa_normalize_f32),
@@ -300,6 +300,8 @@ static int plan_bundle_load_impl(const char* path, avsd_plan_bundle** out) {
             return fail("avsd_guided_step history tables are 4 entries of 4 bytes");   // the entry point reads up to n_hist <= 4
           } else if (c.fn == "avsd_guided_multistep" && n != 0 && n != 16) {
             return fail("avsd_guided_multistep history tables are 4 entries of 4 bytes");
+          } else if (c.fn == "avsd_guided_unipc" && n != 0 && n != 16) {
+            return fail("avsd_guided_unipc history tables are 4 entries of 4 bytes");
           }
         } else if (a.tag != 'S') return fail("unknown argument tag");
       }

@@ -15,7 +15,7 @@ from typing import Optional
 import torch
 
 from . import ops
-from .schedulers import MultistepPlan
+from .schedulers import MultistepPlan, UniPCPlan
 
 
 class DenoiseEngine:
@@ -105,6 +105,7 @@ class DenoiseEngine:
         self._plans = [self.scheduler.plan_step(i) for i in range(self.scheduler.num_forwards())]
         self._hist = torch.zeros((4,) + tuple(latents.shape), dtype=torch.float32, device=dev)
         self._saved = torch.empty_like(latents)
+        self._x_last = torch.zeros_like(latents)       # UniPC: the corrected sample, base of the next step's corrector
 
     def step(self, latents: torch.Tensor, i: int) -> None:
         """One denoising step in place on `latents` (b, 4, F, H, W) f32: UNet on the CFG batch, then the guidance mix
@@ -114,6 +115,11 @@ class DenoiseEngine:
         if isinstance(p, MultistepPlan):        # DPM-Solver++: the ring holds data predictions
             ops.guided_multistep(noise, self.n_branch, self.g, latents, latents, p.ca, p.c_cur, p.s_x, p.s_e, hist=self._hist,
                                  store_slot=p.store_slot, hist_idx=p.hist_idx, w=p.hist_w, g2=self.g2)
+            return
+        if isinstance(p, UniPCPlan):            # UniPC: corrector of the sample the UNet saw, then predictor, one launch
+            ops.guided_unipc(noise, self.n_branch, self.g, latents, latents, self._x_last, p.use_corrector, p.s_x, p.s_e, p.cc_last,
+                             p.cc_cur, p.cp_x, p.cp_cur, hist=self._hist, store_slot=p.store_slot, hist_idx=p.hist_idx, wc=p.wc,
+                             wp=p.wp, g2=self.g2)
             return
         if p.save_sample:                       # StepPlan: PNDM / DDIM
             ops.copy(latents, self._saved)

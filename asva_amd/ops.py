@@ -1303,6 +1303,38 @@ def guided_multistep(noise_pred: torch.Tensor, n_branch: int, g: float, x_in: to
           "avsd_guided_multistep")
 
 
+def guided_unipc(noise_pred: torch.Tensor, n_branch: int, g: float, x_in: torch.Tensor, x_out: torch.Tensor, x_last: torch.Tensor,
+                 use_corrector: bool, s_x: float, s_e: float, cc_last: float, cc_cur: float, cp_x: float, cp_cur: float, *,
+                 hist: Optional[torch.Tensor] = None, store_slot: int = -1, hist_idx=(), wc=(), wp=(), g2: float = 0.0) -> None:
+    """avsd_guided_unipc (include/avsd.h): one UniPC step (corrector of x_in from x_last, then predictor), x_out in place or out of
+    place; `x_last` receives the corrected sample and aliases neither; `hist` is (slots, *x_in.shape)."""
+    _req(noise_pred, F32, "noise_pred")
+    _req(x_in, F32, "x_in")
+    _req(x_out, F32, "x_out")
+    _req(x_last, F32, "x_last")
+    B, Cc, Fr, H, W = x_in.shape
+    if not (x_in.is_contiguous() and x_out.is_contiguous() and x_last.is_contiguous() and x_out.shape == x_in.shape
+            and x_last.shape == x_in.shape and noise_pred.is_contiguous() and noise_pred.numel() == n_branch * x_in.numel()):
+        raise ValueError("guided_unipc: contiguous x_in / x_out / x_last of one shape and noise_pred of n_branch times their size")
+    nbytes = x_in.numel() * 4
+    if any(abs(x_last.data_ptr() - t.data_ptr()) < nbytes for t in (x_in, x_out)):
+        raise ValueError("guided_unipc: x_last must not overlap x_in or x_out")
+    nh = len(hist_idx)
+    if nh > 4 or len(wc) != nh or len(wp) != nh:
+        raise ValueError("guided_unipc: at most 4 history entries, with one wc and one wp weight each")
+    slots = [s for s in (store_slot, *hist_idx) if s >= 0]
+    if slots and (hist is None or not hist.is_contiguous() or hist.dtype != F32 or hist.device != x_in.device
+                  or tuple(hist.shape[1:]) != tuple(x_in.shape) or max(slots) >= hist.shape[0] or min(hist_idx, default=0) < 0):
+        raise ValueError(f"guided_unipc: slots {slots} need a contiguous f32 hist of shape (> {max(slots)}, {tuple(x_in.shape)})")
+    idx = (C.c_int32 * 4)(*(list(hist_idx) + [0] * (4 - nh)))
+    wcs = (C.c_float * 4)(*(list(wc) + [0.0] * (4 - nh)))
+    wps = (C.c_float * 4)(*(list(wp) + [0.0] * (4 - nh)))
+    check(_lib.lib().avsd_guided_unipc(_p(noise_pred), n_branch, float(g), float(g2), _p(hist), store_slot, idx, wcs, wps, nh,
+                                       _p(x_in), _p(x_out), _p(x_last), int(bool(use_corrector)), float(s_x), float(s_e),
+                                       float(cc_last), float(cc_cur), float(cp_x), float(cp_cur), B, Cc, Fr, H * W, _stream()),
+          "avsd_guided_unipc")
+
+
 def vae_postprocess(rows: torch.Tensor, n_img: int, H: int, W: int) -> torch.Tensor:
     _req(rows, P.ACT, "rows")
     out = torch.empty((n_img, 3, H, W), dtype=F32, device=rows.device)

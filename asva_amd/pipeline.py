@@ -26,7 +26,7 @@ import torch
 from . import dist as adist
 from .conditioning import AUDIO_TOKENS, audio_segment_mask
 from .engine import DenoiseEngine
-from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler, PNDMScheduler
+from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler, PNDMScheduler, UniPCMultistepScheduler
 from .unet import AudioUNet3DConditionModel
 from .vae import AutoencoderKL
 from .audio_features import AudioMelspectrogramExtractor
@@ -198,7 +198,8 @@ class AudioCondAnimationPipeline:
         latents = self.prepare_video_latents(image_latents, self.unet.config.in_channels, video_length, height, width, device,
                                              f32, generator, noise)                                      # (b, 4, f, h, w)
 
-        if self.use_engine and isinstance(self.scheduler, (PNDMScheduler, DDIMScheduler, DPMSolverMultistepScheduler)):
+        if self.use_engine and isinstance(self.scheduler, (PNDMScheduler, DDIMScheduler, DPMSolverMultistepScheduler,
+                                                               UniPCMultistepScheduler)):
             ekey = (id(self.unet), id(self.scheduler), float(audio_guidance_scale), float(text_guidance_scale))
             if getattr(self, "_engine_key", None) != ekey:      # keep the engine (and its captured graph) across clips
                 self._engine = DenoiseEngine(self.unet, self.scheduler, audio_guidance_scale, text_guidance_scale)

@@ -241,6 +241,21 @@ def export_multistep_steps(path: str, timesteps, plans) -> None:
                                 len(p.hist_idx), *[int(i) for i in idx], *[float(x) for x in w]))
 
 
+def export_unipc_steps(path: str, timesteps, plans) -> None:
+    """The scalar schedule of a UniPC run (schedulers.UniPCPlan: coefficients of avsd_guided_unipc) as the binary table
+    tools/plan_host.cpp's `denoise_unipc` reads: per step  f32 t, s_x, s_e, cc_last, cc_cur, cp_x, cp_cur; i32 use_corrector,
+    store_slot, n_hist; i32 hist_idx[4]; f32 wc[4]; f32 wp[4]  (88 bytes)."""
+    with open(path, "wb") as f:
+        for t, p in zip(timesteps, plans):
+            nh = len(p.hist_idx)
+            idx = list(p.hist_idx) + [0] * (4 - nh)
+            wc = list(p.wc) + [0.0] * (4 - nh)
+            wp = list(p.wp) + [0.0] * (4 - nh)
+            f.write(struct.pack("<7f3i4i8f", float(t), float(p.s_x), float(p.s_e), float(p.cc_last), float(p.cc_cur), float(p.cp_x),
+                                float(p.cp_cur), int(p.use_corrector), int(p.store_slot), nh, *[int(i) for i in idx],
+                                *[float(x) for x in wc], *[float(x) for x in wp]))
+
+
 class Bundle:
     """A saved bundle, replayed in-process through the C API (what tools/plan_host.cpp does from C++)."""
 

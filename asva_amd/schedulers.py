@@ -15,6 +15,9 @@ into one launch and keeps the eps history on the device.
 
 DPMSolverMultistepScheduler (DPM-Solver++ 1M / 2M / 3M, restated from diffusers 0.29.2 the same way) offers the same two
 forms; its fast path is `plan_step` + `ops.guided_multistep` (avsd_guided_multistep), whose ring holds data predictions.
+
+UniPCMultistepScheduler (UniPC: DPM-Solver++-style predictor plus a corrector that reuses the next step's model output) has
+the same two forms; its fast path is `plan_step` + `ops.guided_unipc` (avsd_guided_unipc): corrector and predictor in one launch.
 """
 from __future__ import annotations
 
@@ -61,6 +64,27 @@ class MultistepPlan:
     store_slot: int = -1      # ring slot to store d in (-1: do not store)
     hist_idx: Tuple[int, ...] = ()
     hist_w: Tuple[float, ...] = ()
+
+
+@dataclass
+class UniPCPlan:
+    """Everything avsd_guided_unipc needs for one scheduler step (UniPC): with d = s_x * x + s_e * eps the data prediction of the
+    sample x the UNet saw and h_k = hist[hist_idx[k]],
+        xc = use_corrector ? cc_last * x_last + cc_cur * d + sum_k wc[k] * h_k : x          (and x_last = xc afterwards)
+        x' = cp_x * xc + cp_cur * d + sum_k wp[k] * h_k."""
+    s_x: float                # d = s_x * x + s_e * eps: 1 / alpha_t and -sigma_t / alpha_t
+    s_e: float
+    use_corrector: bool
+    cc_last: float            # corrector: coefficient of the previous corrected sample
+    cc_cur: float             # corrector: coefficient of this step's data prediction
+    cp_x: float               # predictor: coefficient of the corrected sample
+    cp_cur: float             # predictor: coefficient of this step's data prediction
+    store_slot: int = -1      # ring slot that receives d AFTER the reads (-1: no later step reads it)
+    hist_idx: Tuple[int, ...] = ()
+    wc: Tuple[float, ...] = ()            # one weight per hist_idx entry for the corrector (0: the predictor alone uses it)
+    wp: Tuple[float, ...] = ()            # ... and for the predictor
+    order: int = 1                        # order of this step's predictor
+    corrector_order: int = 0              # order of this step's corrector (0: none)
 
 
 class _Output:
@@ -243,7 +267,52 @@ class PNDMScheduler(_Base):
         return _Output(prev_sample) if return_dict else (prev_sample,)
 
 
-class DPMSolverMultistepScheduler:
+class _SigmaTables:
+    """What DPMSolverMultistepScheduler and UniPCMultistepScheduler share: the timestep / sigma tables of a run."""
+
+    def _build_tables(self, num_inference_steps: int, device=None):
+        """timesteps and the float32-rounded sigma table (n + 1 entries: the last one is the final sigma) from timestep_spacing,
+        steps_offset, use_karras_sigmas and final_sigmas_type, as diffusers' multistep schedulers' set_timesteps builds them"""
+        n, T = num_inference_steps, self.num_train_timesteps
+        if self.timestep_spacing == "linspace":
+            ts = np.linspace(0, T - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
+        elif self.timestep_spacing == "leading":
+            ts = (np.arange(0, n + 1) * (T // (n + 1))).round()[::-1][:-1].copy().astype(np.int64) + self.steps_offset
+        else:
+            ts = np.arange(T, 0, -T / n).round().copy().astype(np.int64) - 1
+        train = ((1.0 - self.acp) / self.acp) ** 0.5
+        if self.use_karras_sigmas:
+            # Karras et al. 2022 (eq. 5, rho = 7) from the schedule's sigma_max down to its sigma_min; timesteps interpolated in log sigma
+            rho, lo, hi = 7.0, train[0], train[-1]
+            sig = (hi ** (1 / rho) + np.linspace(0, 1, n) * (lo ** (1 / rho) - hi ** (1 / rho))) ** rho
+            ts = self._sigma_to_t(sig, np.log(train)).round().astype(np.int64)
+        else:
+            sig = np.interp(ts, np.arange(len(train)), train)
+        last = train[0] if self.final_sigmas_type == "sigma_min" else 0.0
+        self.sigmas = np.concatenate([sig, [last]]).astype(np.float32).astype(np.float64)    # diffusers keeps the table in float32
+        self._ts = [int(t) for t in ts]
+        self.num_inference_steps = len(self._ts)
+        self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
+
+    @staticmethod
+    def _sigma_to_t(sigma, log_sigmas):
+        log_sigma = np.log(np.maximum(sigma, 1e-10))
+        low = np.cumsum(log_sigma - log_sigmas[:, None] >= 0, axis=0).argmax(axis=0).clip(max=log_sigmas.shape[0] - 2)
+        lo, hi = log_sigmas[low], log_sigmas[low + 1]
+        w = np.clip((lo - log_sigma) / (lo - hi), 0, 1)
+        return (1 - w) * low + w * (low + 1)
+
+    @staticmethod
+    def _alpha_sigma(sigma: float) -> Tuple[float, float]:
+        alpha_t = 1.0 / math.sqrt(sigma * sigma + 1.0)
+        return alpha_t, sigma * alpha_t
+
+    def _lambda(self, i: int) -> float:
+        alpha_t, sigma_t = self._alpha_sigma(float(self.sigmas[i]))
+        return math.log(alpha_t) - math.log(sigma_t)
+
+
+class DPMSolverMultistepScheduler(_SigmaTables):
     """DPM-Solver++ (Lu et al. 2022, arXiv:2211.01095), multistep, orders 1-3, restated from diffusers 0.29.2's
     `DPMSolverMultistepScheduler` (`set_timesteps`, `convert_model_output`, `dpm_solver_first_order_update`,
     `multistep_dpm_solver_second_order_update`, `multistep_dpm_solver_third_order_update`, `step`) for the deterministic
@@ -326,50 +395,14 @@ class DPMSolverMultistepScheduler:
         return sample
 
     def set_timesteps(self, num_inference_steps: int, device=None):
-        n, T = num_inference_steps, self.num_train_timesteps
-        if self.timestep_spacing == "linspace":
-            ts = np.linspace(0, T - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
-        elif self.timestep_spacing == "leading":
-            ts = (np.arange(0, n + 1) * (T // (n + 1))).round()[::-1][:-1].copy().astype(np.int64) + self.steps_offset
-        else:
-            ts = np.arange(T, 0, -T / n).round().copy().astype(np.int64) - 1
-        train = ((1.0 - self.acp) / self.acp) ** 0.5
-        if self.use_karras_sigmas:
-            # Karras et al. 2022 (eq. 5, rho = 7) from the schedule's sigma_max down to its sigma_min; timesteps interpolated in log sigma
-            rho, lo, hi = 7.0, train[0], train[-1]
-            sig = (hi ** (1 / rho) + np.linspace(0, 1, n) * (lo ** (1 / rho) - hi ** (1 / rho))) ** rho
-            ts = self._sigma_to_t(sig, np.log(train)).round().astype(np.int64)
-        else:
-            sig = np.interp(ts, np.arange(len(train)), train)
-        last = train[0] if self.final_sigmas_type == "sigma_min" else 0.0
-        self.sigmas = np.concatenate([sig, [last]]).astype(np.float32).astype(np.float64)    # diffusers keeps the table in float32
-        self._ts = [int(t) for t in ts]
-        self.num_inference_steps = len(self._ts)
-        self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
+        self._build_tables(num_inference_steps, device)
         # object-protocol state
         self.model_outputs: List[Optional[torch.Tensor]] = [None] * self.solver_order
         self.lower_order_nums = 0
         self._step_index: Optional[int] = None
 
-    @staticmethod
-    def _sigma_to_t(sigma, log_sigmas):
-        log_sigma = np.log(np.maximum(sigma, 1e-10))
-        low = np.cumsum(log_sigma - log_sigmas[:, None] >= 0, axis=0).argmax(axis=0).clip(max=log_sigmas.shape[0] - 2)
-        lo, hi = log_sigmas[low], log_sigmas[low + 1]
-        w = np.clip((lo - log_sigma) / (lo - hi), 0, 1)
-        return (1 - w) * low + w * (low + 1)
-
     def num_forwards(self) -> int:
         return len(self._ts)
-
-    @staticmethod
-    def _alpha_sigma(sigma: float) -> Tuple[float, float]:
-        alpha_t = 1.0 / math.sqrt(sigma * sigma + 1.0)
-        return alpha_t, sigma * alpha_t
-
-    def _lambda(self, i: int) -> float:
-        alpha_t, sigma_t = self._alpha_sigma(float(self.sigmas[i]))
-        return math.log(alpha_t) - math.log(sigma_t)
 
     def _coeffs(self, i: int):
         """x' = ca x + c0 D0 + c1 D1 + c2 D2 for the step sigmas[i] -> sigmas[i + 1], and the ratios r0 = h_0 / h, r1 = h_1 / h of
@@ -442,6 +475,236 @@ class DPMSolverMultistepScheduler:
             D1 = D1_0 + (r0 / (r0 + r1)) * (D1_0 - D1_1)
             D2 = (1.0 / (r0 + r1)) * (D1_0 - D1_1)
             prev_sample = ca * sample + c0 * m[-1] + c1 * D1 + c2 * D2
+        self.lower_order_nums = min(self.lower_order_nums + 1, self.solver_order)
+        self._step_index += 1
+        return _Output(prev_sample) if return_dict else (prev_sample,)
+
+
+class UniPCMultistepScheduler(_SigmaTables):
+    """UniPC (Zhao et al. 2023, arXiv:2302.04867): a unified predictor-corrector on the data predictions, orders 1-3, variants
+    bh1 / bh2, restated from the paper's update (its Algorithm 5-8 with B(h) = h or e^h - 1) and from diffusers 0.29.2's
+    `UniPCMultistepScheduler` (`set_timesteps`, `convert_model_output`, `multistep_uni_p_bh_update`,
+    `multistep_uni_c_bh_update`, `step`) for `predict_x0=True` on an epsilon-predicting model.
+
+    Notation as in DPMSolverMultistepScheduler (sigma, alpha_t, sigma_t, lambda).  One update from s to t with h = lambda_t -
+    lambda_s, base sample x, m0 the data prediction at s, earlier data predictions m_k at lambda_s + r_k h (r_k < 0) and,
+    for the corrector only, the data prediction m_t at t (r = 1):
+
+        x_t = (sigma_t / sigma_s) x - alpha_t (e^-h - 1) m0 - alpha_t B(-h) sum_k rho_k (m_k - m0) / r_k
+
+    where rho solves R rho = b, R[j][k] = r_k^j and b_j = (-h) phi_{j+2}(-h) (j+1)! / B(-h)  (j = 0, 1, ...).
+
+    Step i (n forwards for n steps; the UNet saw the PREDICTED sample x_i):
+      * m_i = (x_i - sigma_t eps) / alpha_t, from that uncorrected sample;
+      * corrector (i > 0, unless i - 1 is in `disable_corrector`): from sigmas[i - 1] to sigmas[i], base the previous CORRECTED
+        sample, m0 = m_{i-1}, the m_k before it and m_t = m_i, at the order the previous predictor used.  It costs no forward;
+      * predictor: from sigmas[i] to sigmas[i + 1], base the corrected sample, m0 = m_i, at order
+        min(solver_order, n - i if lower_order_final, i + 1).  The last output is a prediction with no corrector after it.
+
+    The fast path (`plan_step` + `ops.guided_unipc`) folds guidance, m_i, both updates and frame-0 pinning into one launch.
+    m_j lives in ring slot j % solver_order; the kernel reads m_{i-1} .. m_{i-solver_order} before m_i replaces the oldest, and
+    the corrected sample stays in the engine's x_last buffer.  Coefficients (and the small R rho = b solve) are float64 on the
+    host.
+
+    Choices that cannot be checked here (diffusers is absent):
+      * the beta schedule defaults to SD1.5's (scaled_linear 0.00085..0.012) as in the other schedulers here, not to diffusers'
+        linear 0.0001..0.02; `from_pretrained` / `from_config` take whatever the configuration says.
+      * diffusers evaluates a step's scalars as float32 tensors; here they are float64 from the float32 sigma table.
+      * rho is fixed to 0.5 for the order-2 predictor and the order-1 corrector and solved from R rho = b otherwise, as
+        diffusers does.
+      * `disable_corrector` lists the steps whose OUTPUT is not corrected: the corrector that runs during step i is skipped when
+        i - 1 is listed (diffusers tests `step_index - 1`).
+      * the last predictor step onto sigma 0 has infinite h: it is first order there and returns the data prediction.  With
+        lower_order_final=False and final_sigmas_type="zero" the order is forced to 1 at that step, as
+        DPMSolverMultistepScheduler does (diffusers' own arithmetic gives 0 * inf there for bh1).
+      * Karras sigmas end on sigma_min, so with final_sigmas_type="sigma_min" the last predictor step has h = 0: it leaves
+        the corrected sample unchanged.
+      * `step()` keeps a copy of the sample as `last_sample` when no corrector ran; diffusers keeps the caller's tensor
+        itself, which a caller that writes the result back into the same storage (the reference-style loop does, on the
+        frames-1.. view) would overwrite before the next corrector reads it.
+      * from_config maps another class's solver_type ("midpoint" / "heun" of a DPM-Solver++ configuration) to "bh2", as
+        diffusers' constructor does; the constructor itself refuses them.
+    Every other option that changes the samples (predict_x0=False, thresholding, v- / sample prediction, solver_p,
+    rescale_betas_zero_snr, trained_betas, other final_sigmas_type) raises NotImplementedError, and so do unknown keys.
+    """
+
+    order = 1
+    init_noise_sigma = 1.0
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
+                 trained_betas=None, solver_order=2, prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995,
+                 sample_max_value=1.0, predict_x0=True, solver_type="bh2", lower_order_final=True, disable_corrector=(),
+                 solver_p=None, use_karras_sigmas=False, timestep_spacing="linspace", steps_offset=0, final_sigmas_type="zero",
+                 rescale_betas_zero_snr=False, **unknown):
+        if not predict_x0 or prediction_type != "epsilon":
+            raise NotImplementedError("only predict_x0=True with prediction_type='epsilon' is restated")
+        if solver_order not in (1, 2, 3) or solver_type not in ("bh1", "bh2"):
+            raise NotImplementedError(f"solver_order {solver_order!r} / solver_type {solver_type!r}: orders 1-3, bh1 or bh2")
+        if final_sigmas_type not in ("zero", "sigma_min") or timestep_spacing not in ("linspace", "leading", "trailing"):
+            raise NotImplementedError(f"final_sigmas_type {final_sigmas_type!r} / timestep_spacing {timestep_spacing!r}")
+        if thresholding or solver_p is not None or rescale_betas_zero_snr or trained_betas is not None:
+            raise NotImplementedError("thresholding / solver_p / rescale_betas_zero_snr / trained_betas are not restated")
+        # keys of the PNDM / DDIM / DPM-Solver++ configurations that UniPC does not have (diffusers ignores them as well)
+        known_inert = {"skip_prk_steps", "set_alpha_to_one", "clip_sample", "clip_sample_range", "algorithm_type", "euler_at_final",
+                       "use_lu_lambdas", "lambda_min_clipped", "variance_type"}
+        bad = sorted(k for k in unknown if not k.startswith("_") and k not in known_inert)
+        if bad:
+            raise NotImplementedError(f"unknown scheduler options {bad}")
+        self.num_train_timesteps = num_train_timesteps
+        self.solver_order, self.solver_type, self.lower_order_final = solver_order, solver_type, lower_order_final
+        self.disable_corrector = [int(i) for i in disable_corrector]
+        self.final_sigmas_type, self.use_karras_sigmas = final_sigmas_type, use_karras_sigmas
+        self.timestep_spacing, self.steps_offset = timestep_spacing, steps_offset
+        self.acp = alphas_cumprod(num_train_timesteps, beta_start, beta_end, beta_schedule)
+        self.num_inference_steps: Optional[int] = None
+        self.timesteps: Optional[torch.Tensor] = None
+        self.sigmas: Optional[np.ndarray] = None
+        self.config = dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                           beta_schedule=beta_schedule, solver_order=solver_order, prediction_type=prediction_type,
+                           predict_x0=True, solver_type=solver_type, lower_order_final=lower_order_final,
+                           disable_corrector=list(self.disable_corrector), use_karras_sigmas=use_karras_sigmas,
+                           final_sigmas_type=final_sigmas_type, timestep_spacing=timestep_spacing, steps_offset=steps_offset)
+
+    @classmethod
+    def from_pretrained(cls, path: str, subfolder: Optional[str] = None):
+        return cls.from_config(_read_config(path, subfolder))
+
+    @classmethod
+    def from_config(cls, config, **overrides):
+        """diffusers' `UniPCMultistepScheduler.from_config(pipe.scheduler.config)`: another scheduler's configuration, with its own
+        keys (PNDM's skip_prk_steps, DPM-Solver++'s algorithm_type, ...) accepted and ignored and its solver_type mapped to bh2."""
+        cfg = {k: v for k, v in dict(config).items() if not k.startswith("_")}
+        if cfg.get("solver_type") in ("midpoint", "heun", "logrho"):
+            cfg["solver_type"] = "bh2"
+        return cls(**{**cfg, **overrides})
+
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        self._build_tables(num_inference_steps, device)
+        # object-protocol state
+        self.model_outputs: List[Optional[torch.Tensor]] = [None] * self.solver_order
+        self.last_sample: Optional[torch.Tensor] = None
+        self.lower_order_nums = 0
+        self.this_order = 0
+        self._step_index: Optional[int] = None
+
+    def num_forwards(self) -> int:
+        return len(self._ts)
+
+    # ---- one update's scalars ---------------------------------------------------------------------------------------------
+    def _update(self, s0: int, t: int, prev: Tuple[int, ...], corrector: bool):
+        """The update from sigmas[s0] to sigmas[t] with earlier data predictions at the table entries `prev` (newest first):
+        x_t = ratio x + a0 m0 + ab sum_k rhos[k] (m_k - m0) / rks[k], the corrector's last k being m_t with rks = 1.
+        None when h = 0 (the update is the identity)."""
+        alpha_t, sigma_t = self._alpha_sigma(float(self.sigmas[t]))
+        sigma_s0 = self._alpha_sigma(float(self.sigmas[s0]))[1]
+        lam_s0 = self._lambda(s0)
+        h = self._lambda(t) - lam_s0
+        if h == 0.0:
+            return None
+        order = len(prev) + 1
+        rks = [(self._lambda(j) - lam_s0) / h for j in prev] + [1.0]
+        hh = -h
+        h_phi_1 = math.expm1(hh)                   # h phi_1(h) = e^h - 1 at hh = -h (data prediction)
+        B_h = hh if self.solver_type == "bh1" else h_phi_1
+        h_phi_k, fact, b = h_phi_1 / hh - 1.0, 1.0, []
+        for k in range(1, order + 1):
+            b.append(h_phi_k * fact / B_h)
+            fact *= k + 1
+            h_phi_k = h_phi_k / hh - 1.0 / fact
+        R = np.array([[r ** (k - 1) for r in rks] for k in range(1, order + 1)], dtype=np.float64)
+        b = np.array(b, dtype=np.float64)
+        if corrector:
+            rhos = [0.5] if order == 1 else [float(v) for v in np.linalg.solve(R, b)]
+        elif order == 1:
+            rhos = []
+        else:
+            rhos = [0.5] if order == 2 else [float(v) for v in np.linalg.solve(R[:-1, :-1], b[:-1])]
+        return sigma_t / sigma_s0, -alpha_t * h_phi_1, -alpha_t * B_h, rks, rhos
+
+    def _order(self, i: int, warm: Optional[int] = None) -> int:
+        """order of step i's predictor; `warm` = data predictions seen before this step (i when the run starts at step 0)"""
+        n = len(self._ts)
+        k = min(self.solver_order, n - i) if self.lower_order_final else self.solver_order
+        k = min(k, (i if warm is None else warm) + 1)
+        if i == n - 1 and float(self.sigmas[n]) in (0.0, float(self.sigmas[n - 1])):
+            k = 1                                  # onto sigma 0 (h infinite), or h = 0: nothing but m_i enters
+        return k
+
+    def _corrects(self, i: int) -> bool:
+        return i > 0 and (i - 1) not in self.disable_corrector
+
+    def _reads(self, j: int) -> set:
+        """table entries whose data prediction step j reads from the ring"""
+        got = set(range(j - self._order(j) + 1, j))
+        if self._corrects(j):
+            got |= set(range(j - self._order(j - 1), j))
+        return got
+
+    def plan_step(self, i: int) -> UniPCPlan:
+        """Step i as coefficients of avsd_guided_unipc: both updates folded into per-slot weights.  m_j lives in ring slot
+        j % solver_order; m_i is stored (after the reads) only when a later step reads it."""
+        n = len(self._ts)
+        alpha_s, sigma_s = self._alpha_sigma(float(self.sigmas[i]))
+        w = {}                                     # table entry j < i -> [corrector weight, predictor weight] of m_j
+        cc_last = cc_cur = 0.0
+        q = self._order(i - 1) if self._corrects(i) else 0
+        if q:
+            ratio, a0, ab, rks, rhos = self._update(i - 1, i, tuple(i - 1 - k for k in range(1, q)), corrector=True)
+            cc_last, cc_cur = ratio, ab * rhos[-1]
+            w.setdefault(i - 1, [0.0, 0.0])[0] += a0 - ab * sum(rho / r for rho, r in zip(rhos, rks))
+            for k in range(1, q):
+                w.setdefault(i - 1 - k, [0.0, 0.0])[0] += ab * rhos[k - 1] / rks[k - 1]
+        p = self._order(i)
+        zero = float(self.sigmas[i + 1]) == 0.0
+        up = None if zero else self._update(i, i + 1, tuple(i - k for k in range(1, p)), corrector=False)
+        if zero:                                   # h infinite: the data prediction itself (alpha_t = 1)
+            cp_x, cp_cur = 0.0, 1.0
+        elif up is None:                           # h = 0
+            cp_x, cp_cur = 1.0, 0.0
+        else:
+            ratio, a0, ab, rks, rhos = up
+            cp_x, cp_cur = ratio, a0 - ab * sum(rho / r for rho, r in zip(rhos, rks))
+            for k in range(1, p):
+                w.setdefault(i - k, [0.0, 0.0])[1] += ab * rhos[k - 1] / rks[k - 1]
+        js = sorted(w, reverse=True)
+        store = i % self.solver_order if any(i in self._reads(j) for j in range(i + 1, min(n, i + self.solver_order + 1))) else -1
+        return UniPCPlan(s_x=1.0 / alpha_s, s_e=-sigma_s / alpha_s, use_corrector=bool(q), cc_last=cc_last, cc_cur=cc_cur,
+                         cp_x=cp_x, cp_cur=cp_cur, store_slot=store, hist_idx=tuple(j % self.solver_order for j in js),
+                         wc=tuple(w[j][0] for j in js), wp=tuple(w[j][1] for j in js), order=p, corrector_order=q)
+
+    # object protocol (tensor-level, any device): diffusers' step, written over the differences D1_k = (m_k - m0) / r_k
+    def _apply(self, u, x, m0, ms):
+        ratio, a0, ab, rks, rhos = u
+        out = ratio * x + a0 * m0
+        for rho, r, mk in zip(rhos, rks, ms):
+            out = out + (ab * rho / r) * (mk - m0)
+        return out
+
+    def step(self, model_output, timestep, sample, return_dict=True, **_):
+        if self._step_index is None:
+            hits = [j for j, t in enumerate(self._ts) if t == int(timestep)]
+            self._step_index = (hits[1] if len(hits) > 1 else hits[0]) if hits else len(self._ts) - 1
+        i = self._step_index
+        alpha_s, sigma_s = self._alpha_sigma(float(self.sigmas[i]))
+        m_t = (sample - sigma_s * model_output) / alpha_s          # from the uncorrected sample the model saw
+        m = [v for v in self.model_outputs if v is not None]       # m_{i-1} last
+        use_corrector = self._corrects(i) and self.last_sample is not None
+        if use_corrector:
+            q = self.this_order
+            u = self._update(i - 1, i, tuple(i - 1 - k for k in range(1, q)), corrector=True)
+            sample = self._apply(u, self.last_sample, m[-1], [m[-1 - k] for k in range(1, q)] + [m_t])
+        self.model_outputs = self.model_outputs[1:] + [m_t]
+        m = m + [m_t]
+        self.this_order = self._order(i, warm=self.lower_order_nums)
+        self.last_sample = sample if use_corrector else sample.clone()
+        if float(self.sigmas[i + 1]) == 0.0:
+            prev_sample = m_t.clone()
+        else:
+            u = self._update(i, i + 1, tuple(i - k for k in range(1, self.this_order)), corrector=False)
+            prev_sample = sample.clone() if u is None else self._apply(u, sample, m_t, [m[-1 - k] for k in range(1, self.this_order)])
         self.lower_order_nums = min(self.lower_order_nums + 1, self.solver_order)
         self._step_index += 1
         return _Output(prev_sample) if return_dict else (prev_sample,)

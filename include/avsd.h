@@ -377,6 +377,24 @@ int avsd_guided_multistep(const float* noise_pred, int n_branch, float g, float 
                           float* x_out, float ca, float c_cur, float s_x, float s_e, int B, int C, int F,
                           int HW, void* stream);
 
+/* Guidance + UniPC step (corrector, then predictor) on (B, C, F, H, W) f32 latents, frame 0 pinned, one launch:
+ *   eps  = guidance combine of noise_pred (n_branch 1 / 2 / 3, g, g2: exactly the rule of avsd_guided_step)
+ *   d    = s_x * x_in + s_e * eps            (data prediction m_i of the PREDICTED sample x_in the UNet just saw)
+ *   h_k  = hist[hist_idx[k]], k < n_hist     (n_hist <= 4; every slot is read before the store below)
+ *   xc   = use_corrector ? cc_last * x_last + cc_cur * d + sum_k wc[k] * h_k : x_in      (the corrected sample)
+ *   hist[store_slot] = d                     (if store_slot >= 0; it may be one of hist_idx: the oldest entry is replaced)
+ *   x_last = xc                              (base of the next call's corrector)
+ *   x_out  = cp_x * xc + cp_cur * d + sum_k wp[k] * h_k                                  (prediction for the next sigma)
+ *   frame 0: x_out = x_in bit-exact, x_last = x_in
+ * One index list serves both sums: a zero in wc or wp marks an entry only the other update uses; slots outside
+ * hist_idx[0..n_hist) are never read.  x_out may alias x_in; x_last may alias neither (AVSD_EINVAL).
+ * asva_amd/schedulers.py UniPCMultistepScheduler computes the coefficients on the host. */
+int avsd_guided_unipc(const float* noise_pred, int n_branch, float g, float g2, float* hist, int store_slot,
+                      const int32_t* hist_idx_host, const float* wc_host, const float* wp_host, int n_hist,
+                      const float* x_in, float* x_out, float* x_last, int use_corrector, float s_x, float s_e,
+                      float cc_last, float cc_cur, float cp_x, float cp_cur, int B, int C, int F, int HW,
+                      void* stream);
+
 /* VAE post-processing (pipeline_audio_cond_animation.py:212): channels-last bf16
  * [N*H*W][ld] (3 channels) -> (N, 3, H, W) f32 = clamp(x / 2 + 0.5, 0, 1). */
 int avsd_vae_postprocess(const void* src, int ld, float* dst, int N, int HW, void* stream);

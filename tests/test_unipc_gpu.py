@@ -1,0 +1,248 @@
+"""UniPC on the MI355X (-m gpu): avsd_guided_unipc against its contract in float64, the engine with and without graph replay,
+10 steps through the engine against the fp32 oracle UNet driven by the scheduler's object protocol, an SD1.5-shaped clip through
+AudioCondAnimationPipeline, and tools/plan_host.cpp running the UniPC loop without Python."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+from tests.helpers import filled_unet, load_golden, rel_l2
+from tests.test_unipc_cpu import guided_unipc as contract
+
+pytestmark = pytest.mark.gpu
+TOL_NORTH_STAR = 1e-3     # BASELINE.json: "outputs within 1e-3 rel-L2 of reference"
+
+
+def _f32(v):
+    return float(np.float32(v))
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+CASES = [  # n_branch, corrector, hist_idx, store_slot
+    (1, False, (), -1),            # nothing but the first-order predictor
+    (1, True, (), 0),              # order-1 corrector with its m0 weight zero: no history entry, a store
+    (2, True, (1,), 1),            # the only entry is overwritten: read before the store
+    (2, False, (0, 2), 3),         # corrector off, store outside hist_idx
+    (3, True, (2, 0, 1), 1),       # three entries, the last (oldest) one overwritten
+    (3, True, (0, 1, 2), 3),       # three entries, store outside
+    (2, True, (3, 1), -1),         # no store
+]
+
+
+@pytest.mark.parametrize("n_branch,corrector,hist_idx,store", CASES)
+@pytest.mark.parametrize("inplace", [False, True])
+def test_guided_unipc_kernel_matches_float64(n_branch, corrector, hist_idx, store, inplace):
+    """B = 2 and HW = 35 (not a multiple of 4).  Every element of x_out, x_last and the stored slot lies within
+    (T + 4) 2^-23 S of the float64 contract: S is the float64 sum of the absolute values of the output's terms with d, the
+    corrected sample and the guided eps written out into the kernel's inputs (a bound on what any rounding in the chain can act
+    on), T the number of products in that written-out sum, + 4 for the guidance mix's own operations — the worst case of an f32
+    FMA chain (2^-24 per rounding, at most T + 4 roundings, a factor 2 to spare).  Slots outside hist_idx hold NaN: none may
+    reach an output; with the corrector off x_last holds NaN on entry."""
+    from asva_amd import ops
+
+    B, C, F, H, W = 2, 4, 5, 5, 7
+    gen = torch.Generator().manual_seed(100 * n_branch + 10 * len(hist_idx) + store + 3)
+    npred = torch.randn(n_branch * B, C, F, H, W, generator=gen)
+    x = torch.randn(B, C, F, H, W, generator=gen)
+    xl = torch.randn(B, C, F, H, W, generator=gen) if corrector else torch.full((B, C, F, H, W), float("nan"))
+    hist = torch.randn(4, B, C, F, H, W, generator=gen)
+    for k in range(4):
+        if k not in hist_idx:
+            hist[k] = float("nan")
+    nh = len(hist_idx)
+    wc = tuple(_f32(v) if corrector else 0.0 for v in torch.randn(nh, generator=gen))
+    wp = tuple(_f32(v) for v in torch.randn(nh, generator=gen))
+    coef = dict(s_x=_f32(1.07), s_e=_f32(-0.38), cc_last=_f32(0.81), cc_cur=_f32(0.23), cp_x=_f32(0.93), cp_cur=_f32(0.41))
+    g, g2 = 4.0, 2.5
+
+    want, want_last, want_hist = torch.empty_like(x, dtype=torch.float64), xl.double(), hist.double()
+    contract(npred.double(), n_branch, g, x.double(), want, want_last, corrector, **coef, hist=want_hist, store_slot=store,
+             hist_idx=hist_idx, wc=wc, wp=wp, g2=g2)
+    # the sums of absolute values, written out
+    e = npred.double().abs().reshape(n_branch, B, C, F, H, W)
+    S_eps = e[0] if n_branch == 1 else e[0] + g * (e[1] + e[0]) + (g2 * (e[2] + e[1]) if n_branch == 3 else 0.0)
+    S_d, T_d = abs(coef["s_x"]) * x.double().abs() + abs(coef["s_e"]) * S_eps, 2
+    hs = [hist[k].double().abs() for k in hist_idx]
+    if corrector:
+        S_c = abs(coef["cc_last"]) * xl.double().abs() + abs(coef["cc_cur"]) * S_d + sum(abs(w) * h for w, h in zip(wc, hs))
+        T_c = 2 + nh + T_d
+    else:
+        S_c, T_c = x.double().abs(), 0
+    S_o = abs(coef["cp_x"]) * S_c + abs(coef["cp_cur"]) * S_d + sum(abs(w) * h for w, h in zip(wp, hs))
+    T_o = 2 + nh + T_c + T_d
+
+    xd, hd, ld = x.cuda(), hist.cuda(), xl.cuda()
+    out = xd if inplace else torch.empty_like(xd)
+    ops.guided_unipc(npred.cuda(), n_branch, g, xd, out, ld, corrector, **coef, hist=hd if (store >= 0 or nh) else None,
+                     store_slot=store, hist_idx=hist_idx, wc=wc, wp=wp, g2=g2)
+    torch.cuda.synchronize()
+    out, ld, hd = out.cpu(), ld.cpu(), hd.cpu()
+    u = 2.0 ** -23
+    assert bool(torch.isfinite(out).all()) and bool(torch.isfinite(ld).all())
+    assert bool(((out.double() - want).abs() <= (T_o + 4) * u * S_o).all())
+    assert torch.equal(out[:, :, 0], x[:, :, 0])                              # frame 0 pinned, bit-exact
+    assert torch.equal(ld[:, :, 0], x[:, :, 0])
+    if corrector:
+        assert bool(((ld.double() - want_last).abs() <= (T_c + 4) * u * S_c).all())
+    else:
+        assert torch.equal(ld, x)                                             # the uncorrected sample itself
+    for k in range(4):
+        if k == store:
+            assert bool(((hd[k].double() - want_hist[k]).abs() <= (T_d + 4) * u * S_d).all())
+        else:
+            assert torch.equal(_bits(hd[k]), _bits(hist[k]))                  # other slots untouched, bit for bit
+
+
+def test_ops_guided_unipc_refuses_bad_arguments():
+    from asva_amd import ops
+
+    x = torch.zeros(1, 4, 2, 3, 3, device="cuda")
+    n = torch.zeros(2, 4, 2, 3, 3, device="cuda")
+    hist = torch.zeros(2, 1, 4, 2, 3, 3, device="cuda")
+    c = (True, 1.0, -0.5, 0.9, 0.1, 0.8, 0.2)
+    with pytest.raises(ValueError, match="overlap"):
+        ops.guided_unipc(n, 2, 4.0, x, x, x, *c)
+    with pytest.raises(ValueError, match="slots"):
+        ops.guided_unipc(n, 2, 4.0, x, x, torch.zeros_like(x), *c, hist=hist, store_slot=2)
+    with pytest.raises(ValueError, match="slots"):
+        ops.guided_unipc(n, 2, 4.0, x, x, torch.zeros_like(x), *c, hist=None, hist_idx=(0,), wc=(1.0,), wp=(1.0,))
+    with pytest.raises(ValueError, match="one wc and one wp"):
+        ops.guided_unipc(n, 2, 4.0, x, x, torch.zeros_like(x), *c, hist=hist, hist_idx=(0,), wc=(1.0,), wp=())
+    with pytest.raises(ValueError, match="contiguous"):
+        ops.guided_unipc(n[:1], 2, 4.0, x, x, torch.zeros_like(x), *c)
+
+
+def _tiny(order=2, use_graph=True, unet=None):
+    from asva_amd.engine import DenoiseEngine
+    from asva_amd.schedulers import UniPCMultistepScheduler
+
+    g = load_golden("unet_tiny_e2e.pt")
+    unet = unet if unet is not None else filled_unet(g["config"]).to("cuda")
+    eng = DenoiseEngine(unet, UniPCMultistepScheduler(solver_order=order), audio_guidance_scale=4.0, use_graph=use_graph)
+    f = g["sample"].shape[2]
+    eng.set_conditioning(g["text"][:1].cuda(), g["audio"][1:2].cuda(), g["audio"][:1].cuda(), g["mask"], f)
+    return eng, unet
+
+
+@pytest.mark.parametrize("order", [2, 3])
+def test_engine_graph_replay_is_bit_identical(order):
+    g = load_golden("unet_tiny_e2e.pt")
+    lat = torch.randn(1, 4, *g["sample"].shape[2:], generator=torch.Generator().manual_seed(4)).cuda()
+    eager, unet = _tiny(order, use_graph=False)
+    a = eager.run(lat, 8)
+    replay, _ = _tiny(order, use_graph=True, unet=unet)
+    b = replay.run(lat, 8)
+    c = replay.run(lat, 8)
+    torch.cuda.synchronize()
+    assert torch.equal(a, b) and torch.equal(b, c)
+    assert torch.equal(a[:, :, 0], lat[:, :, 0]) and not torch.equal(a, lat) and bool(torch.isfinite(a).all())
+
+
+def test_unipc_10_steps_through_engine_against_fp32_oracle():
+    """The tiny golden UNet in split precision (and bf16) through the engine, UniPC-2 bh2 for 10 steps, audio guidance 4.0, against
+    the fp32 oracle UNet (oracle/unet_ref.py) driven by the same class's object protocol with the guidance in torch"""
+    from asva_amd import precision as P
+    from asva_amd.engine import DenoiseEngine
+    from asva_amd.schedulers import UniPCMultistepScheduler
+    from oracle.unet_ref import unet_forward
+
+    g = load_golden("unet_tiny_e2e.pt")
+    f, h, w = g["sample"].shape[2:]
+    lat = torch.randn(1, 4, f, h, w, generator=torch.Generator().manual_seed(7))
+    lat[:, :, 0] *= 0.18215
+    text, audio, null_audio = g["text"][:1], g["audio"][1:2], g["audio"][:1]
+    ref_unet = filled_unet(g["config"])
+    sd, cfg = {k: v.clone() for k, v in ref_unet.state_dict().items()}, dict(ref_unet.config)
+    sch = UniPCMultistepScheduler()
+    sch.set_timesteps(10)
+    txt = torch.cat([text, text])[:, None].expand(-1, f, -1, -1)
+    aud = torch.cat([null_audio, audio])[:, None].expand(-1, f, -1, -1)
+    m = g["mask"][None].expand(2, -1, -1)
+    want = lat.clone()
+    for t in sch.timesteps:
+        n0, n1 = unet_forward(sd, cfg, torch.cat([want, want]), int(t), txt, aud, m).chunk(2)
+        eps = n0 + 4.0 * (n1 - n0)
+        want[:, :, 1:] = sch.step(eps[:, :, 1:], t, want[:, :, 1:]).prev_sample
+    errs = {}
+    for mode in ("bf16x2", "bf16"):
+        P.set_split(mode == "bf16x2")
+        try:
+            eng = DenoiseEngine(filled_unet(g["config"]).to("cuda"), UniPCMultistepScheduler(), audio_guidance_scale=4.0)
+            eng.set_conditioning(text.cuda(), audio.cuda(), null_audio.cuda(), g["mask"], f)
+            got = eng.run(lat.cuda(), 10)
+            torch.cuda.synchronize()
+        finally:
+            P.set_split(False)
+        assert torch.equal(got[:, :, 0].cpu(), lat[:, :, 0])
+        errs[mode] = rel_l2(got, want)
+    print("UniPC-2 bh2, 10 steps, engine vs fp32 oracle loop: " + ", ".join(f"{k} {v:.3e}" for k, v in errs.items()))
+    assert errs["bf16x2"] < TOL_NORTH_STAR
+    assert errs["bf16"] < 3.4e-2       # regression guard, 1.5 x the measured 2.22e-2 (split precision: 3.6e-5)
+
+
+def test_sd15_clip_through_pipeline_unipc_10_steps():
+    """An SD1.5-shaped 12 x 32 x 32 clip through AudioCondAnimationPipeline with UniPC-2 bh2, 10 steps, audio guidance 4.0: the fused
+    engine (hipGraph replay + one avsd_guided_unipc per step) and the reference-style loop"""
+    from asva_amd.conditioning import audio_segment_mask
+    from asva_amd.pipeline import AudioCondAnimationPipeline, synthetic_clip
+    from asva_amd.schedulers import UniPCMultistepScheduler
+    from tests.test_configs_gpu import _cfg
+
+    dev = torch.device("cuda")
+    pipe = AudioCondAnimationPipeline(unet=filled_unet(_cfg()), scheduler=UniPCMultistepScheduler(), vae=None).to(dev)
+    pipe.set_progress_bar_config(disable=True)
+    c = synthetic_clip(0, device=dev)
+    kw = dict(texts=[""], text_encodings=[c["text_encodings"][None]], image_latents=c["image_latents"][None], noise=c["noise"][None],
+              audio_encodings=c["audio_encodings"][None], null_audio_encodings=c["null_audio_encodings"][None],
+              audio_masks=audio_segment_mask(12), num_inference_steps=10, audio_guidance_scale=4.0, output_latents=True)
+    fused = pipe(**kw)
+    assert fused.shape == (1, 4, 12, 32, 32) and bool(torch.isfinite(fused).all())
+    assert torch.equal(fused[:, :, 0], c["image_latents"][None])
+    pipe.use_engine = False
+    looped = pipe(**kw)
+    err = rel_l2(fused, looped)
+    print(f"SD1.5-shaped clip, UniPC-2 bh2 10 steps: engine vs reference-style loop rel-L2 {err:.3e}")
+    assert err < 4.0e-2                # regression guard, 1.5 x the measured 2.62e-2.  Not zero for the reason given in
+                                       # test_dpmsolver_gpu.py::test_sd15_clip_through_pipeline_dpmsolver_20_steps: the engine's shared
+                                       # guidance prefix sums rows in another f32 order; the tile choice is deterministic
+
+
+@pytest.mark.parametrize("graph", ["0", "1"])
+def test_cpp_host_runs_the_unipc_loop_without_python(tmp_path, graph):
+    """test_dpmsolver_gpu.py::test_cpp_host_runs_the_dpmsolver_loop_without_python for UniPC-2, 10 steps: the table written by
+    plan.export_unipc_steps, plan_host's `denoise_unipc` — latents byte-identical to the Python engine's"""
+    from asva_amd import _lib, build, plan
+    from asva_amd.engine import DenoiseEngine
+    from asva_amd.schedulers import UniPCMultistepScheduler
+    from tests.test_plan_gpu import _bytes, _record
+
+    assert os.path.exists(build.PLAN_HOST), "asva_amd/plan_host not built (python -m asva_amd.build)"
+    r = _record(tmp_path, "ddim", steps=2)
+    g, lat0 = r["g"], r["lat0"]
+    eng = DenoiseEngine(r["unet"], UniPCMultistepScheduler(), audio_guidance_scale=4.0, use_graph=False)
+    eng.set_conditioning(g["text"][:1].cuda(), g["audio"][1:2].cuda(), g["audio"][:1].cuda(), g["mask"], lat0.shape[2])
+    want = eng.run(lat0, 10)
+    torch.cuda.synchronize()
+    plan.export_unipc_steps(str(tmp_path / "steps_unipc.bin"), eng._ts.tolist(), eng._plans)
+    for name, tns in (("text", r["text"]), ("audio", r["audio"]), ("latents", lat0)):
+        _bytes(tns).cpu().numpy().tofile(str(tmp_path / f"{name}.in"))
+    b, c, f, h, w = r["shape"]
+    prog = tmp_path / "program.txt"
+    prog.write_text(
+        f"load text {tmp_path}/text.in\nload audio {tmp_path}/audio.in\nload latents {tmp_path}/latents.in\n"
+        "run set_conditioning\n"
+        f"denoise_unipc {tmp_path}/steps_unipc.bin latents x t noise_pred 2 4.0 0.0 {b} {c} {f} {h * w}\n"
+        f"save latents {tmp_path}/latents.out\n")
+    out = subprocess.run([build.PLAN_HOST, _lib.LIB_PATHS["bf16"], r["path"], str(prog)], capture_output=True, text=True, timeout=300,
+                         env=dict(os.environ, PLAN_HOST_GRAPH=graph))
+    print(out.stdout[-600:], out.stderr[-600:])
+    assert out.returncode == 0
+    assert "10 denoising steps" in out.stdout
+    got = torch.from_numpy(np.fromfile(str(tmp_path / "latents.out"), dtype=np.float32)).reshape(r["shape"])
+    assert torch.equal(got, want.cpu()), f"max |diff| {float((got - want.cpu()).abs().max()):.3e}"
+    assert torch.equal(got[:, :, 0], lat0[:, :, 0].cpu())

@@ -5,7 +5,8 @@ AVSync classifier (asva_amd/avsync.py): raw scores, and RelSync of the first mod
     python tools/avsync_score.py --clips 4 --modes bf16 plan --steps 20      # the defaults; modes: bf16 fp16 split plan
 
 Without --model the classifier gets seeded random weights and the numbers mean nothing: the run then only shows that the path works
-and what it costs.  The UNet and VAE are the SD1.5-shaped random-weight models of tools/clip_bench.py (DPM-Solver++ 2M sampling)."""
+and what it costs.  The UNet and VAE are the SD1.5-shaped random-weight models of tools/clip_bench.py (DPM-Solver++ 2M sampling;
+--scheduler unipc: UniPC-2)."""
 import argparse
 import os
 import sys
@@ -19,7 +20,7 @@ from asva_amd import avsync, precision  # noqa: E402
 from asva_amd.audio_features import waveform_to_melspectrogram  # noqa: E402
 from asva_amd.conditioning import audio_segment_mask  # noqa: E402
 from asva_amd.pipeline import AudioCondAnimationPipeline, synthetic_clip  # noqa: E402
-from asva_amd.schedulers import DPMSolverMultistepScheduler  # noqa: E402
+from asva_amd.schedulers import DPMSolverMultistepScheduler, UniPCMultistepScheduler  # noqa: E402
 from asva_amd.vae import AutoencoderKL  # noqa: E402
 
 MODES = {"bf16": lambda: precision.set_precision("bf16"), "fp16": lambda: precision.set_precision("fp16"),
@@ -64,6 +65,7 @@ def main():
     ap.add_argument("--modes", nargs=2, default=["bf16", "plan"], choices=sorted(MODES))
     ap.add_argument("--model", default=None, help="directory with audio_encoder/ video_encoder/ head/ of a trained AVSync classifier")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--scheduler", choices=("dpmsolver++", "unipc"), default="dpmsolver++")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
 
@@ -74,7 +76,7 @@ def main():
         unet = bench.build_unet(dev, 0, 1)                       # the same seed, so the same weights, in every mode
         with torch.device(dev):
             vae = AutoencoderKL().eval()
-        sched = DPMSolverMultistepScheduler()
+        sched = UniPCMultistepScheduler() if args.scheduler == "unipc" else DPMSolverMultistepScheduler()
         pipe = AudioCondAnimationPipeline(unet=unet, scheduler=sched, vae=vae).to(dev)
         pipe.set_progress_bar_config(disable=True)
         out = []

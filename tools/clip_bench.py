@@ -3,24 +3,26 @@ forwards, audio guidance 4.0) through AudioCondAnimationPipeline: SD1.5-shaped U
 weights, synthetic conditioning.  Reports per-clip latency split into denoising and VAE decode.
 
     python tools/clip_bench.py                                     # PNDM-50, the reference's schedule
-    python tools/clip_bench.py --scheduler dpmsolver++ --steps 20  # DPM-Solver++ (2M), 20 UNet forwards"""
+    python tools/clip_bench.py --scheduler dpmsolver++ --steps 20  # DPM-Solver++ (2M), 20 UNet forwards
+    python tools/clip_bench.py --scheduler unipc --steps 10        # UniPC (order 2, bh2), 10 UNet forwards"""
 import argparse, sys, os, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench
 from asva_amd.pipeline import AudioCondAnimationPipeline, synthetic_clip
-from asva_amd.schedulers import DDIMScheduler, DPMSolverMultistepScheduler, PNDMScheduler
+from asva_amd.schedulers import DDIMScheduler, DPMSolverMultistepScheduler, PNDMScheduler, UniPCMultistepScheduler
 from asva_amd.vae import AutoencoderKL
 from asva_amd.conditioning import audio_segment_mask
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--scheduler", choices=("pndm", "ddim", "dpmsolver++"), default="pndm")
+ap.add_argument("--scheduler", choices=("pndm", "ddim", "dpmsolver++", "unipc"), default="pndm")
 ap.add_argument("--steps", type=int, default=50)
 args = ap.parse_args()
-sched = {"pndm": PNDMScheduler, "ddim": DDIMScheduler, "dpmsolver++": DPMSolverMultistepScheduler}[args.scheduler]()
+sched = {"pndm": PNDMScheduler, "ddim": DDIMScheduler, "dpmsolver++": DPMSolverMultistepScheduler,
+         "unipc": UniPCMultistepScheduler}[args.scheduler]()
 sched.set_timesteps(args.steps)
 n_fwd = sched.num_forwards()
-label = {"pndm": "PNDM", "ddim": "DDIM", "dpmsolver++": "DPM++ 2M"}[args.scheduler]
+label = {"pndm": "PNDM", "ddim": "DDIM", "dpmsolver++": "DPM++ 2M", "unipc": "UniPC-2"}[args.scheduler]
 
 dev = torch.device("cuda", 0)
 unet = bench.build_unet(dev, 0, 1)

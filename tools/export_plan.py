@@ -1,9 +1,10 @@
 """Writes a launch-plan bundle (include/avsd.h "launch plans", asva_amd/plan.py) for the AVSync15 geometry of BASELINE.json
 configs[1]: SD1.5 UNet3D (random-init, seeded), one 12 x 256 x 256 clip, audio-only guidance (CFG batch 2), 50-step PLMS
-table (--scheduler ddim / dpmsolver++: DDIM or DPM-Solver++; the latter writes steps_ms.bin for plan_host's `denoise_ms`), SD1.5
+table (--scheduler ddim / dpmsolver++ / unipc: DDIM, DPM-Solver++ or UniPC; the last two write steps_ms.bin / steps_unipc.bin for
+plan_host's `denoise_ms` / `denoise_unipc`), SD1.5
 VAE decode — and the program file that makes tools/plan_host.cpp run the whole clip without Python.
 
-    python tools/export_plan.py --out /tmp/avsync15 [--steps 50] [--no-vae] [--scheduler {pndm,ddim,dpmsolver++}] [--solver-order 2]
+    python tools/export_plan.py --out /tmp/avsync15 [--steps 50] [--no-vae] [--scheduler {pndm,ddim,dpmsolver++,unipc}] [--solver-order 2]
     asva_amd/plan_host asva_amd/libavsd_hip.so /tmp/avsync15/clip.plan /tmp/avsync15/program.txt
 
 Also runs the same clip through the Python DenoiseEngine and stores its final latents / frames (expected.*.bin) so the two
@@ -27,8 +28,8 @@ def main():
     ap.add_argument("--out", default="/tmp/avsync15")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--no-vae", action="store_true")
-    ap.add_argument("--scheduler", choices=("pndm", "ddim", "dpmsolver++"), default="pndm")
-    ap.add_argument("--solver-order", type=int, default=2, help="DPM-Solver++ order (1, 2 or 3)")
+    ap.add_argument("--scheduler", choices=("pndm", "ddim", "dpmsolver++", "unipc"), default="pndm")
+    ap.add_argument("--solver-order", type=int, default=2, help="DPM-Solver++ / UniPC order (1, 2 or 3)")
     ap.add_argument("--check", default=None, help="compare <dir>/latents.out, frames.out (written by plan_host) with expected.*.bin")
     a = ap.parse_args()
     if a.check:
@@ -45,7 +46,7 @@ def main():
     from asva_amd import plan, precision as P, unet as U
     from asva_amd.conditioning import audio_segment_mask
     from asva_amd.engine import DenoiseEngine
-    from asva_amd.schedulers import DDIMScheduler, DPMSolverMultistepScheduler, PNDMScheduler
+    from asva_amd.schedulers import DDIMScheduler, DPMSolverMultistepScheduler, PNDMScheduler, UniPCMultistepScheduler
 
     dev = torch.device("cuda", 0)
     os.makedirs(a.out, exist_ok=True)
@@ -89,6 +90,8 @@ def main():
     b.close()
     if a.scheduler == "dpmsolver++":
         sched = DPMSolverMultistepScheduler(solver_order=a.solver_order)
+    elif a.scheduler == "unipc":
+        sched = UniPCMultistepScheduler(solver_order=a.solver_order)
     else:
         sched = PNDMScheduler() if a.scheduler == "pndm" else DDIMScheduler()
     eng = DenoiseEngine(unet, sched, audio_guidance_scale=4.0)
@@ -96,6 +99,9 @@ def main():
     if a.scheduler == "dpmsolver++":
         steps_file, denoise = "steps_ms.bin", "denoise_ms"
         plan.export_multistep_steps(os.path.join(a.out, steps_file), eng._ts.tolist(), eng._plans)
+    elif a.scheduler == "unipc":
+        steps_file, denoise = "steps_unipc.bin", "denoise_unipc"
+        plan.export_unipc_steps(os.path.join(a.out, steps_file), eng._ts.tolist(), eng._plans)
     else:
         steps_file, denoise = "steps.bin", "denoise"
         plan.export_steps(os.path.join(a.out, steps_file), eng._ts.tolist(), eng._plans)

@@ -16,6 +16,9 @@
 //   denoise_ms <steps_ms.bin> <latents> <x> <t> <noise> <n_branch> <g> <g2> <B> <C> <F> <HW>
 //                                              the same loop with a DPM-Solver++ table (asva_amd/plan.py:
 //                                              export_multistep_steps): the update is avsd_guided_multistep
+//   denoise_unipc <steps_unipc.bin> <latents> <x> <t> <noise> <n_branch> <g> <g2> <B> <C> <F> <HW>
+//                                              the same loop with a UniPC table (asva_amd/plan.py: export_unipc_steps): the
+//                                              update is avsd_guided_unipc, corrector and predictor in one launch
 //   copy <src> <dst> <bytes>                   device-to-device between regions
 //   save <region> <file>                       download a region to a file
 // <latents>, <x>, <t>, <noise> and the names after load / save / copy are REGION names of the bundle.
@@ -59,6 +62,7 @@ struct Api {
   decltype(&avsd_plan_run) run;
   decltype(&avsd_guided_step) guided_step;
   decltype(&avsd_guided_multistep) guided_multistep;
+  decltype(&avsd_guided_unipc) guided_unipc;
   decltype(&avsd_copy) copy;
 };
 
@@ -85,6 +89,14 @@ struct MsStep {
   int32_t store_slot, n_hist;
   int32_t hist_idx[4];
   float hist_w[4];
+};
+
+// one entry of the UniPC table (asva_amd/plan.py: export_unipc_steps; schedulers.UniPCPlan)
+struct UniPCStep {
+  float t, s_x, s_e, cc_last, cc_cur, cp_x, cp_cur;
+  int32_t use_corrector, store_slot, n_hist;
+  int32_t hist_idx[4];
+  float wc[4], wp[4];
 };
 
 static std::vector<unsigned char> read_file(const std::string& path) {
@@ -122,6 +134,7 @@ int main(int argc, char** argv) {
   sym(h, "avsd_plan_run", api.run);
   sym(h, "avsd_guided_step", api.guided_step);
   sym(h, "avsd_guided_multistep", api.guided_multistep);
+  sym(h, "avsd_guided_unipc", api.guided_unipc);
   sym(h, "avsd_copy", api.copy);
 #define AVSD_OK_OR_DIE(x)                                                              \
   do {                                                                                 \
@@ -218,21 +231,23 @@ int main(int argc, char** argv) {
       long long bytes;
       ss >> s >> d >> bytes;
       AVSD_OK_OR_DIE(api.copy(reg(s).ptr, reg(d).ptr, bytes, 1, stream));
-    } else if (cmd == "denoise" || cmd == "denoise_ms") {
-      const bool dpm = cmd == "denoise_ms";
+    } else if (cmd == "denoise" || cmd == "denoise_ms" || cmd == "denoise_unipc") {
+      const bool dpm = cmd == "denoise_ms", unipc = cmd == "denoise_unipc";
       std::string file, lat, x, t, noise;
       int n_branch, B, Cc, Fr, HW;
       float g, g2;
       ss >> file >> lat >> x >> t >> noise >> n_branch >> g >> g2 >> B >> Cc >> Fr >> HW;
       const std::vector<unsigned char> raw = read_file(file);
-      const size_t n = raw.size() / (dpm ? sizeof(MsStep) : sizeof(Step));
+      const size_t n = raw.size() / (unipc ? sizeof(UniPCStep) : dpm ? sizeof(MsStep) : sizeof(Step));
       const Step* steps = reinterpret_cast<const Step*>(raw.data());
       const MsStep* ms_steps = reinterpret_cast<const MsStep*>(raw.data());
+      const UniPCStep* up_steps = reinterpret_cast<const UniPCStep*>(raw.data());
       const int64_t lat_bytes = (int64_t)B * Cc * Fr * HW * 4;
       float *hist = nullptr, *saved = nullptr;
       HIP_OK(hipMalloc(&hist, (size_t)(4 * lat_bytes)));
       HIP_OK(hipMemset(hist, 0, (size_t)(4 * lat_bytes)));
-      HIP_OK(hipMalloc(&saved, (size_t)lat_bytes));
+      HIP_OK(hipMalloc(&saved, (size_t)lat_bytes));   // PLMS: the saved sample; UniPC: x_last, the corrected sample
+      HIP_OK(hipMemset(saved, 0, (size_t)lat_bytes));
       float* latents = reinterpret_cast<float*>(reg(lat).ptr);
       unsigned char *xp = reg(x).ptr, *tp = reg(t).ptr;
       const float* np_ = reinterpret_cast<const float*>(reg(noise).ptr);
@@ -240,8 +255,8 @@ int main(int argc, char** argv) {
         fprintf(stderr, "plan_host: denoise: B x C x F x HW does not match the latent regions\n");
         return 1;
       }
-      if (dpm && (n_branch < 1 || reg(noise).bytes < n_branch * lat_bytes)) {
-        fprintf(stderr, "plan_host: denoise_ms: region %s holds fewer than %d noise predictions\n", noise.c_str(), n_branch);
+      if ((dpm || unipc) && (n_branch < 1 || reg(noise).bytes < n_branch * lat_bytes)) {
+        fprintf(stderr, "plan_host: %s: region %s holds fewer than %d noise predictions\n", cmd.c_str(), noise.c_str(), n_branch);
         return 1;
       }
       const int kf = plan("forward");
@@ -263,9 +278,23 @@ int main(int argc, char** argv) {
       HIP_OK(hipEventRecord(e0, stream));
       for (size_t i = 0; i < n; ++i) {
         AVSD_OK_OR_DIE(api.copy(latents, xp, lat_bytes, 1, stream));
-        HIP_OK(hipMemcpyAsync(tp, dpm ? &ms_steps[i].t : &steps[i].t, 4, hipMemcpyHostToDevice, stream));
+        HIP_OK(hipMemcpyAsync(tp, unipc ? &up_steps[i].t : dpm ? &ms_steps[i].t : &steps[i].t, 4, hipMemcpyHostToDevice, stream));
         if (gexec) HIP_OK(hipGraphLaunch(gexec, stream));
         else AVSD_OK_OR_DIE(api.run(b, kf, stream));
+        if (unipc) {
+          const UniPCStep& u = up_steps[i];
+          bool ok = u.store_slot < 4 && u.n_hist >= 0 && u.n_hist <= 4;
+          for (int k = 0; ok && k < u.n_hist; ++k) ok = u.hist_idx[k] >= 0 && u.hist_idx[k] < 4;
+          if (!ok) {
+            fprintf(stderr, "plan_host: %s step %zu names a history slot outside the 4-slot ring\n", file.c_str(), i);
+            return 1;
+          }
+          AVSD_OK_OR_DIE(api.guided_unipc(np_, n_branch, g, g2, hist, u.store_slot, u.n_hist ? u.hist_idx : nullptr,
+                                          u.n_hist ? u.wc : nullptr, u.n_hist ? u.wp : nullptr, u.n_hist, latents, latents, saved,
+                                          u.use_corrector, u.s_x, u.s_e, u.cc_last, u.cc_cur, u.cp_x, u.cp_cur, B, Cc, Fr, HW,
+                                          stream));
+          continue;
+        }
         if (dpm) {
           const MsStep& m = ms_steps[i];
           bool ok = m.store_slot < 4 && m.n_hist >= 0 && m.n_hist <= 4;
