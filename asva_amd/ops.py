@@ -1179,6 +1179,55 @@ def qproj_attention(h: torch.Tensor, stats: torch.Tensor, wq: torch.Tensor, q_co
     return out
 
 
+def ff_block_supported(M: int, C: int, with_proj_out: bool = True) -> bool:
+    """GEGLU projection + FF-out (+ proj_out) of a transformer block as one launch (avsd_ff_block): where it is built and measured
+    faster than the launches it replaces"""
+    return not P.SPLIT and bool(_lib.lib().avsd_ff_block_supported(M, C, int(with_proj_out)))
+
+
+def ff_block(h: torch.Tensor, stats: torch.Tensor, w1_frag: torch.Tensor, w1_colsum: torch.Tensor, b1: torch.Tensor,
+             w2_frag: torch.Tensor, b2: torch.Tensor, wp_frag: Optional[torch.Tensor] = None, bp: Optional[torch.Tensor] = None,
+             x: Optional[torch.Tensor] = None, *, eps: float = 1e-5, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = (GEGLU(LN(h) W1'^T + b1) W2^T + b2 + h) Wp^T + bp + x in one launch, or without wp_frag the inner h' alone; see
+    avsd_ff_block (include/avsd.h).  The three weights come in MFMA-fragment order (weights.pack_frag), W1' packed for GEGLU with the
+    LayerNorm gain folded in, w1_colsum / b1 as the LayerNorm-folded GEMM takes them; stats [M, C / 32, 2] or pre-folded [M, 1, 2]."""
+    if P.SPLIT:
+        raise ValueError("ff_block: not built for split precision (use the separate kernels)")
+    _req(h, P.ACT, "h")
+    _req(stats, F32, "stats")
+    for t, nm in ((w1_frag, "w1_frag"), (w2_frag, "w2_frag")) + (((wp_frag, "wp_frag"),) if wp_frag is not None else ()):
+        _req(t, P.ACT, nm)
+    for t, nm in ((w1_colsum, "w1_colsum"), (b1, "b1"), (b2, "b2")) + (((bp, "bp"),) if bp is not None else ()):
+        _req(t, F32, nm)
+    if h.dim() != 2:
+        raise ValueError("ff_block: h must be [M, C]")
+    M, Cc = h.shape
+    if (not w1_frag.is_contiguous() or not w2_frag.is_contiguous() or w1_frag.numel() != 8 * Cc * Cc or w2_frag.numel() != 4 * Cc * Cc
+            or w1_colsum.numel() != 8 * Cc or b1.numel() != 8 * Cc or b2.numel() != Cc
+            or not (w1_colsum.is_contiguous() and b1.is_contiguous() and b2.is_contiguous())):
+        raise ValueError("ff_block: w1_frag [8 C / 32, C / 16, 64, 8] with w1_colsum [8 C], b1 [8 C]; w2_frag [C / 32, 4 C / 16, 64, 8] with b2 [C]")
+    if not stats.is_contiguous() or stats.dim() != 3 or stats.shape[0] != M or stats.shape[2] != 2:
+        raise ValueError("ff_block: stats must be contiguous f32 [M, C / 32 or 1, 2]")
+    if wp_frag is not None:
+        if bp is None or x is None:
+            raise ValueError("ff_block: wp_frag goes with bp and x")
+        _req(x, P.ACT, "x")
+        if not wp_frag.is_contiguous() or wp_frag.numel() != Cc * Cc or bp.numel() != Cc or not bp.is_contiguous() or x.shape != (M, Cc):
+            raise ValueError("ff_block: wp_frag [C / 32, C / 16, 64, 8] with bp [C] and x [M, C]")
+    if out is None:
+        out = torch.empty((M, Cc), dtype=P.ACT, device=h.device)
+    _req(out, P.ACT, "out")
+    if out.shape != (M, Cc):
+        raise ValueError("ff_block: out must be [M, C]")
+    proj = wp_frag is not None
+    a_ = (_p(h), _ld(h), _p(stats), int(stats.shape[1]), float(eps), _p(w1_frag), _p(w1_colsum), _p(b1), _p(w2_frag), _p(b2),
+          _p(wp_frag), _p(bp) if proj else None, _p(x) if proj else None, _ld(x) if proj else 0, _p(out), _ld(out), M, Cc)
+    _timed("ff_block", (24.0 + (2.0 if proj else 0.0)) * M * Cc * Cc, _nbytes(h, out, x if proj else None) + (24.0 + (2.0 if proj else 0.0)) * Cc * Cc,
+           (h, stats, w1_frag, w1_colsum, b1, w2_frag, b2, wp_frag, bp, x, out),
+           lambda: check(_lib.lib().avsd_ff_block(*a_, _stream()), "avsd_ff_block"))
+    return out
+
+
 def temporal_attention(qkv: torch.Tensor, *, b: int, frames: int, hw: int, heads: int,
                        scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _req(qkv, P.ACT, "qkv")

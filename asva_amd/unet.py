@@ -49,6 +49,9 @@ _FUSE_XATTN = True
 # below 32 x 32 (C = 640 / 1280), where the one-launch block is not built: Q projection + cross-attention as one launch
 # (avsd_qproj_attention), the output projection stays a GEMM.  AVSD_FUSE_QATTN=0 runs the three launches, for A/B runs.
 _FUSE_QATTN = os.environ.get("AVSD_FUSE_QATTN", "1") != "0"
+# at 32 x 32 (C = 320): GEGLU projection + FF-out + proj_out of a transformer block as one launch (avsd_ff_block): g and h' stay on
+# the chip.  AVSD_FUSE_FF=0 runs the three launches, for A/B runs.
+_FUSE_FF = os.environ.get("AVSD_FUSE_FF", "1") != "0"
 # the GEGLU projection re-folds the K / 32 LayerNorm partials of its rows in each of its 20-80 column tiles (+8-10 us per launch): fold
 # them once in a tiny launch (avsd_ln_fold) and hand it one pair per row
 _LN_PREFOLD = True
@@ -416,6 +419,10 @@ class Packer(Blob):
             # Decided by the MODE, not by the tensor: a layout-only (meta) replica must register the same items as the rank that holds
             # the weights, or the two blobs differ in size and offsets (asva_amd.dist.broadcast_blob)
             p.w1_ln_f = reg(pack_frag(w1_ln))
+            if p.dim == 320:
+                # FF-out and proj_out in the same order for the one-launch block tail (csrc/ffblock.hip; ops.ff_block_supported)
+                p.w2_f = reg(pack_frag(self.items[p.ff2.w.idx]))
+                p.wp_f = reg(pack_frag(self.items[p.proj_out.w.idx]))
         if p.audio:
             p.norm_audio = self.aff(b.norm_audio)
             p.attn_audio = self.attn(b.attn_audio, False, b.norm_audio)
@@ -1174,6 +1181,10 @@ def _transformer(st, x: _Act, p, hw, heads, split: int = 1, rest=False) -> _Act:
     # 5. GEGLU feed-forward, activation fused in the first GEMM's epilogue (:361-371)
     if fused:
         wf = getattr(p, "w1_ln_f", None)
+        if (_FUSE_FF and wf is not None and hasattr(p, "w2_f") and not P.SPLIT and not st.f32_stream and not rest and P.PLAN is None
+                and ops.ff_block_supported(M, C, True)):
+            # one launch for the three products: g and h' never leave the chip (csrc/ffblock.hip)
+            return _Act(ops.ff_block(h.lo, stats[si], wf, p.s1_ln, p.b1_ln, p.w2_f, p.ff2.b, p.wp_f, p.proj_out.b, x.lo, eps=eps))
         if wf is not None and ops._NSTREAM and not P.SPLIT and ops.nstream_supported(M, 8 * C, C):
             # A-resident tile: every wave folds the statistics of its own rows once — no avsd_ln_fold launch
             g = ops.gemm(h.lo, p.w1_ln, bias=p.b1_ln, geglu=True, ln=(stats[si], p.s1_ln, eps), w_frag=wf)

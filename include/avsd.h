@@ -250,6 +250,22 @@ int avsd_sizeof_xattn_desc(void);
 int avsd_qproj_attention_supported(int C, int heads, int lk_pad, int rows_per_kv_block);
 int avsd_qproj_attention(const avsd_xattn_desc* desc_host, void* stream);
 
+/* The tail of a 320-channel transformer block as one launch (csrc/ffblock.hip), in place of three GEMMs:
+ *     g   = GEGLU(LayerNorm(h) . W1'^T + b1)      [M][4 C]   (AVSD_GEMM_LNFUSE | AVSD_GEMM_GEGLU, W1' packed for GEGLU)
+ *     h'  = g . W2^T + b2 + h                     [M][C]
+ *     out = h' . Wp^T + bp + x                    [M][C]     (wp_frag == NULL: out = h', and bp, x are ignored)
+ * h, x, out: 16-bit rows with leading dimensions ldh, ldx, ldo (multiples of 8); ln_stats: the f32 [M][ln_nblk][2] row statistics of
+ * h (ln_nblk = C / 32, or 1: pre-folded), w1_colsum / b1 as ln_colsum / bias of the folded projection; w1_frag [8 C / 32][C / 16][64][8],
+ * w2_frag [C / 32][4 C / 16][64][8] and wp_frag [C / 32][C / 16][64][8] are the three weights in MFMA-fragment order
+ * (AVSD_GEMM_W_FRAG).  g and h' are rounded to 16 bits as the three launches round them and every product accumulates in f32
+ * over ascending K: bit-identical to them on LDS-direct tiles with the unrotated K walk.  Built for C = 320 in the one-pass
+ * libraries; anything else is AVSD_EINVAL and launches nothing.  avsd_ff_block_supported() tells where it is built AND measured
+ * faster than the launches it replaces (a lower bound on M). */
+int avsd_ff_block_supported(int M, int C, int with_proj_out);
+int avsd_ff_block(const void* h, int ldh, const float* ln_stats, int ln_nblk, float ln_eps, const void* w1_frag, const float* w1_colsum,
+                  const float* b1, const void* w2_frag, const float* b2, const void* wp_frag, const float* bp, const void* x, int ldx,
+                  void* out, int ldo, int M, int C, void* stream);
+
 /* out[M, N] (f32) = act_out( act_in(x[M, K] f32) . W[N, K]^T + bias ), M <= 16.
  * act: 0 none, 1 SiLU.  Time-embedding MLP and the per-ResBlock time_emb_proj
  * (audio_cond_unet_3d_condition.py:673-680, ff_spatio_temp_resnet_3d.py:170), and the
