@@ -22,8 +22,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
-from .weights import Blob, _Pk, pack_device
+from . import f32net, ops
+from .weights import _Pk
 
 CONFIG_NAME = "config.json"
 BIN_NAME = "diffusion_pytorch_model.bin"
@@ -166,9 +166,7 @@ class FCHead(_Pretrained):
 
 # ---- packing: BatchNorm fold + weight re-layout (pure torch, any device: tests/test_avsync_cpu.py applies it with torch ops) -------
 def _bn_affine(bn):
-    """eval-mode BatchNorm as y = s * x + b, in float64"""
-    s = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
-    return s, bn.bias.detach().double() - bn.running_mean.detach().double() * s
+    return f32net.bn_affine(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
 
 
 def _triple(v, fill):
@@ -179,24 +177,13 @@ def _triple(v, fill):
 def fold_conv(conv, scale=None, bias=None, relu: bool = False) -> _Pk:
     """one launch of avsd_convnd_f32: weight * scale[cout] re-laid to [cout][taps][cin] (rows padded with zeros to a multiple of 4
     floats), f32; `scale` / `bias` are float64 [cout] or None"""
-    w = conv.weight.detach().double()
-    if w.dim() == 2:                                    # nn.Linear: a (1, 1, 1) window over a 1 x 1 x 1 "image"
-        w = w[:, :, None, None, None]
+    if isinstance(conv, nn.Linear):                     # a (1, 1, 1) window over a 1 x 1 x 1 "image"
         taps, stride, pad = (1, 1, 1), (1, 1, 1), (0, 0, 0)
         if conv.bias is not None:
             bias = conv.bias.detach().double() if bias is None else bias + conv.bias.detach().double()
     else:
-        if w.dim() == 4:
-            w = w[:, :, None]
         taps, stride, pad = _triple(conv.kernel_size, 1), _triple(conv.stride, 1), _triple(conv.padding, 0)
-    if scale is not None:
-        w = w * scale.view(-1, 1, 1, 1, 1)
-    cout, cin = w.shape[:2]
-    k = taps[0] * taps[1] * taps[2] * cin
-    mat = torch.zeros((cout, (k + 3) // 4 * 4), dtype=torch.float32, device=w.device)
-    mat[:, :k] = w.permute(0, 2, 3, 4, 1).reshape(cout, k).float()
-    return _Pk(w=mat, bias=None if bias is None else bias.float().contiguous(), rscale=None, taps=taps, stride=stride, pad=pad,
-               cin=cin, cout=cout, relu=relu)
+    return f32net.fold_conv(conv.weight, scale, bias, taps=taps, stride=stride, pad=pad, rscale=None, relu=relu)
 
 
 def fold_video(net: VideoR2Plus1DNet) -> _Pk:
@@ -232,14 +219,13 @@ def fold_head(net: FCHead) -> list:
 
 
 # ---- the network as a sequence of launches; `be` supplies conv / maxpool / mean (the device library, or torch ops in the CPU test) --
-class _Hip:
+class _Hip(f32net._HipBase):
     @staticmethod
     def conv(x, layer, res=None):
         return ops.convnd_f32(x, layer.w, layer.taps, layer.stride, layer.pad, bias=layer.bias, res=res,
                               rscale=layer.rscale if res is not None else None, relu=layer.relu)
 
     maxpool = staticmethod(ops.maxpool_hw_f32)
-    mean = staticmethod(ops.mean_rows_f32)
 
 
 def run_video(pk: _Pk, x: torch.Tensor, be=_Hip, stages: Optional[list] = None) -> torch.Tensor:
@@ -277,7 +263,7 @@ def run_head(pk: list, audio_emb: torch.Tensor, video_emb: torch.Tensor, be=_Hip
     return y.view(y.shape[0], -1)
 
 
-class AVSyncClassifier(nn.Module):
+class AVSyncClassifier(f32net.F32Net):
     """avsync_classifier.py:10-33: score = head(audio_encoder(audio), video_encoder(video))[:, 0]"""
 
     def __init__(self, audio_encoder: AudioConv2DNet, video_encoder: VideoR2Plus1DNet, head: FCHead):
@@ -285,48 +271,24 @@ class AVSyncClassifier(nn.Module):
         self.audio_encoder = audio_encoder
         self.video_encoder = video_encoder
         self.head = head
-        self._packed = None
 
     # ---- packing --------------------------------------------------------------------------------------------------------------
-    def _versions(self):
-        return tuple(getattr(m, "_epoch", 0) for m in (self.audio_encoder, self.video_encoder, self.head))
+    # real torch modules underneath: nn.Module's own loader and .to(); a sub-network loaded or moved on its own counts too
+    to = nn.Module.to
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        r = super().load_state_dict(state_dict, strict=strict, **kw)
-        self._packed = None
+        r = nn.Module.load_state_dict(self, state_dict, strict=strict, **kw)
+        self._epoch += 1
         return r
 
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        self._packed = None
-        return r
+    def _pack_epoch(self) -> int:
+        return self._epoch + sum(getattr(m, "_epoch", 0) for m in (self.audio_encoder, self.video_encoder, self.head))
 
-    def pack(self, device=None):
-        """state_dict -> folded f32 kernel layouts inside one device blob; cached, repacked after load_state_dict / .to()"""
-        device = pack_device(device)
-        pk = self._packed
-        if pk is not None and pk.versions == self._versions() and (device is None or pk.blob.device == device):
-            return pk
-        device = pack_device(device, next(self.parameters()).device, ops, "AVSyncClassifier.pack")
+    def _fold(self, state_dict) -> _Pk:
         for m in self.modules():
             if isinstance(m, nn.modules.batchnorm._BatchNorm) and m.training:
                 raise RuntimeError("AVSyncClassifier.pack: BatchNorm is folded with its running statistics; call .eval() first")
-        blob = Blob()
-
-        def reg(o):      # every tensor of the folded structure becomes a region of the blob
-            if isinstance(o, _Pk):
-                for k, v in list(o.__dict__.items()):
-                    o.__dict__[k] = blob.reg(v) if isinstance(v, torch.Tensor) else reg(v)
-            elif isinstance(o, list):
-                for v in o:
-                    reg(v)
-            return o
-
-        root = blob.finish(reg(_Pk(video=fold_video(self.video_encoder), audio=fold_audio(self.audio_encoder),
-                                   head=fold_head(self.head))), device)
-        root.versions = self._versions()
-        self._packed = root
-        return root
+        return _Pk(video=fold_video(self.video_encoder), audio=fold_audio(self.audio_encoder), head=fold_head(self.head))
 
     # ---- forward --------------------------------------------------------------------------------------------------------------
     @staticmethod

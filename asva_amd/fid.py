@@ -21,14 +21,13 @@ been measured.
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Optional, Sequence, Tuple, Union
+from typing import Dict, List, Optional, Tuple, Union
 
 import torch
-import torch.nn as nn
 
-from . import ops
+from . import f32net, ops
 from .avsync import _RESIZE
-from .weights import Blob, _Pk, pack_device
+from .weights import _Pk
 
 ENV_WEIGHTS = "AVSD_FID_INCEPTION"
 INPUT_SIZE = 229            # the reference's own number (compute_fid.py:11), not Inception's usual 299
@@ -116,29 +115,14 @@ def _fold(sd, spec, cin_pad: int = 0, cout_pad: int = 0) -> _Pk:
     """BasicConv2d -> one launch: weight * bn scale re-laid [cout][kh][kw][cin] (tap-major, cin-minor), rows padded with zeros to a
     multiple of 4 floats; `cin_pad` / `cout_pad` widen the layer with zero input channels / zero output channels (bias 0: ReLU gives 0)"""
     name, cin, cout, (kh, kw), s, (ph, pw) = spec
-    w = sd[name + ".conv.weight"].detach().double()
+    w = sd[name + ".conv.weight"]
     if tuple(w.shape) != (cout, cin, kh, kw):
         raise ValueError(f"{name}.conv.weight is {tuple(w.shape)}, expected {(cout, cin, kh, kw)}")
-    scale = sd[name + ".bn.weight"].detach().double() / torch.sqrt(sd[name + ".bn.running_var"].detach().double() + BN_EPS)
-    bias = sd[name + ".bn.bias"].detach().double() - sd[name + ".bn.running_mean"].detach().double() * scale
-    w = (w * scale.view(-1, 1, 1, 1)).permute(0, 2, 3, 1)                       # [cout][kh][kw][cin]
-    ci, co = max(cin, cin_pad), max(cout, cout_pad)
-    full = torch.zeros((co, kh, kw, ci), dtype=torch.float64, device=w.device)
-    full[:cout, :, :, :cin] = w
-    k = kh * kw * ci
-    mat = torch.zeros((co, (k + 3) // 4 * 4), dtype=torch.float32, device=w.device)
-    mat[:, :k] = full.reshape(co, k).float()
-    b = torch.zeros(co, dtype=torch.float32, device=w.device)
-    b[:cout] = bias.float()
-    return _Pk(w=mat, bias=b, taps=(1, kh, kw), stride=(1, s, s), pad=(0, ph, pw), cin=ci, cout=co)
+    scale, bias = f32net.bn_affine(*(sd[f"{name}.bn.{leaf}"] for leaf in ("weight", "bias", "running_mean", "running_var")), BN_EPS)
+    return f32net.fold_conv(w, scale, bias, taps=(1, kh, kw), stride=(1, s, s), pad=(0, ph, pw), cin_pad=cin_pad, cout_pad=cout_pad)
 
 
-def _stack(layers: Sequence[_Pk]) -> _Pk:
-    """1 x 1 convolutions on the same input as ONE launch: weight rows and biases one after the other"""
-    a = layers[0]
-    assert all(l.taps == (1, 1, 1) and l.cin == a.cin and l.w.shape[1] == a.w.shape[1] for l in layers)
-    return _Pk(w=torch.cat([l.w for l in layers]), bias=torch.cat([l.bias for l in layers]), taps=a.taps, stride=a.stride, pad=a.pad,
-               cin=a.cin, cout=sum(l.cout for l in layers))
+_stack = f32net.stack_1x1
 
 
 def fold_network(sd) -> _Pk:
@@ -175,20 +159,12 @@ def fold_network(sd) -> _Pk:
 
 
 # ---- the network as a sequence of launches; `be` supplies conv / pool / mean / linear (the device library; torch ops in the CPU test) --
-class _Hip:
-    empty = staticmethod(lambda shape, like: torch.empty(shape, dtype=torch.float32, device=like.device))
-
+class _Hip(f32net._HipBase):
     @staticmethod
     def conv(x, layer, out=None):
         return ops.convnd_ld_f32(x, layer.w, layer.taps, layer.stride, layer.pad, out=out, bias=layer.bias, relu=True)
 
     pool = staticmethod(ops.pool3_hw_f32)
-    mean = staticmethod(ops.mean_rows_f32)
-
-    @staticmethod
-    def linear(x, w, b):
-        m = x.shape[0]
-        return ops.convnd_f32(x.view(m, 1, 1, 1, -1), w, (1, 1, 1), (1, 1, 1), (0, 0, 0), bias=b).view(m, -1)
 
 
 def _out_hw(h, w, layer):
@@ -274,7 +250,7 @@ def run_network(pk: _Pk, x: torch.Tensor, last_block: int = 3, be=_Hip, stages: 
 
 
 # ---- the module -----------------------------------------------------------------------------------------------------------------------
-class InceptionV3(nn.Module):
+class InceptionV3(f32net.F32Net):
     """inception_v3.py:16-150.  `output_blocks`: 0 first max pool (64 maps), 1 second max pool (192), 2 Mixed_6e (768), 3 the final
     average pool (B, 2048), 4 the classifier (B, 1008).  Parameters are created uninitialised: load a state dict."""
 
@@ -290,84 +266,11 @@ class InceptionV3(nn.Module):
         if not self.output_blocks or self.output_blocks[0] < 0 or self.output_blocks[-1] > 4:
             raise ValueError(f"output_blocks must be indices 0 .. 4, got {tuple(output_blocks)}")
         self.last_needed_block = self.output_blocks[-1]
-        for key, shape in state_dict_shapes().items():
-            mod, parts = self, key.split(".")
-            for p in parts[:-1]:
-                if p not in mod._modules:
-                    mod.add_module(p, nn.Module())
-                mod = mod._modules[p]
-            if parts[-1] == "num_batches_tracked":
-                mod.register_buffer(parts[-1], torch.zeros(shape, dtype=torch.int64))
-            elif parts[-1] in ("running_mean", "running_var"):
-                mod.register_buffer(parts[-1], torch.empty(shape, dtype=torch.float32))
-            else:
-                mod.register_parameter(parts[-1], nn.Parameter(torch.empty(shape, dtype=torch.float32), requires_grad=False))
-        self._packed: Optional[_Pk] = None
-        self._epoch = 0
-        self.requires_grad_(False)
+        f32net.declare(self, state_dict_shapes())
         self.eval()
 
-    @property
-    def device(self) -> torch.device:
-        return next(self.parameters()).device
-
-    def to(self, *args, **kw):
-        """moves to a device; dtype=torch.float32 is accepted, any other dtype refused: the metric computes in f32 only"""
-        device, dtype = kw.get("device"), kw.get("dtype")
-        for a in args:
-            if isinstance(a, torch.dtype):
-                dtype = a
-            elif isinstance(a, (str, torch.device, int)):
-                device = a
-        if dtype not in (None, torch.float32):
-            raise ValueError(f"InceptionV3 computes in float32 only, got dtype={dtype}")
-        if device is not None:
-            super().to(device)
-        return self
-
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        self._epoch += 1
-        return r
-
-    def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        own = super().state_dict()
-        missing = [k for k in own if k not in state_dict and not k.endswith("num_batches_tracked")]
-        if missing:
-            raise KeyError(f"InceptionV3.load_state_dict: the checkpoint lacks {len(missing)} tensors, e.g. {missing[:3]}")
-        unexpected = [k for k in state_dict if k not in own]
-        if strict and unexpected:
-            raise KeyError(f"InceptionV3.load_state_dict: {len(unexpected)} unexpected tensors, e.g. {unexpected[:3]}")
-        for k, p in own.items():
-            if k in state_dict and tuple(state_dict[k].shape) != tuple(p.shape):
-                raise ValueError(f"InceptionV3.load_state_dict: {k!r} is {tuple(state_dict[k].shape)}, expected {tuple(p.shape)}")
-        r = super().load_state_dict({k: state_dict[k].to(own[k].dtype) if k in state_dict else own[k] for k in own}, strict=True)
-        self._epoch += 1
-        return r
-
-    def pack(self, device=None) -> _Pk:
-        """state_dict -> folded f32 kernel layouts inside ONE device blob built by weights.Blob and stamped with the shared pack key;
-        cached, repacked after load_state_dict / .to()"""
-        device = pack_device(device)
-        pk = self._packed
-        if pk is not None and pk.epoch == self._epoch and (device is None or pk.blob.device == device):
-            return pk
-        device = pack_device(device, self.device, ops, "InceptionV3.pack")
-        blob = Blob()
-
-        def reg(o):
-            if isinstance(o, _Pk):
-                for k, v in list(o.__dict__.items()):
-                    o.__dict__[k] = blob.reg(v) if isinstance(v, torch.Tensor) else reg(v)
-            elif isinstance(o, list):
-                for v in o:
-                    reg(v)
-            return o
-
-        root = blob.finish(reg(fold_network(super().state_dict())), device)
-        root.epoch = self._epoch
-        self._packed = root
-        return root
+    def _fold(self, state_dict) -> _Pk:
+        return fold_network(state_dict)
 
     @torch.no_grad()
     def forward(self, inp: torch.Tensor, stages: Optional[dict] = None) -> List[torch.Tensor]:
@@ -391,16 +294,10 @@ def load_inceptionv3_pretrained(block_ids=(3, 4), use_fid_inception: bool = True
     """inception_v3.py:331-332, without its download: `weights` is the path of pytorch-fid's checkpoint
     (pt_inception-2015-12-05-*.pth) or a loaded state dict; without it the environment variable AVSD_FID_INCEPTION names the file."""
     net = InceptionV3(tuple(block_ids), use_fid_inception=use_fid_inception)
-    if weights is None:
-        weights = os.environ.get(ENV_WEIGHTS) or None
-    if weights is None:
-        raise FileNotFoundError("no Inception-v3 checkpoint: pass weights=<path of pytorch-fid's pt_inception-2015-12-05-*.pth, or a state "
-                                f"dict> or set the environment variable {ENV_WEIGHTS}; nothing is downloaded here")
+    weights = f32net.resolve_checkpoint(weights, ENV_WEIGHTS, "Inception-v3 checkpoint",
+                                        "path of pytorch-fid's pt_inception-2015-12-05-*.pth, or a state dict")
     if not isinstance(weights, dict):
-        path = os.fspath(weights)
-        if not os.path.isfile(path):
-            raise FileNotFoundError(f"Inception-v3 checkpoint {path!r} (weights= or ${ENV_WEIGHTS}) does not exist")
-        weights = torch.load(path, map_location="cpu", weights_only=True)
+        weights = torch.load(weights, map_location="cpu", weights_only=True)
     net.load_state_dict(weights)
     return net
 

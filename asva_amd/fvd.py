@@ -24,15 +24,14 @@ time-averaged logits are unverified, and no FVD of a real clip has been measured
 from __future__ import annotations
 
 import os
-from typing import Dict, Optional, Sequence, Tuple, Union
+from typing import Dict, Optional, Tuple, Union
 
 import torch
-import torch.nn as nn
 
-from . import ops
+from . import f32net, ops
 from .avsync import _RESIZE
 from .fid import frechet_distance  # noqa: F401  (the distance FVD uses, re-exported)
-from .weights import Blob, _Pk, pack_device
+from .weights import _Pk
 
 ENV_WEIGHTS = "AVSD_FVD_I3D"
 INPUT_SIZE = 224
@@ -101,30 +100,15 @@ def _fold(sd, spec, bn_eps: float, cin_pad: int = 0, cout_pad: int = 0) -> _Pk:
     """Unit3D -> one launch: weight * bn scale re-laid [cout][kt][kh][kw][cin] (tap-major, cin-minor), rows padded with zeros to a
     multiple of 4 floats; `cin_pad` / `cout_pad` widen the layer with zero input channels / zero output channels (bias 0: ReLU gives 0)"""
     name, cin, cout, k, s = spec
-    w = sd[name + ".conv3d.weight"].detach().double()
+    w = sd[name + ".conv3d.weight"]
     cin = w.shape[1] if name == "Conv3d_1a_7x7" else cin
     if tuple(w.shape) != (cout, cin, *k):
         raise ValueError(f"{name}.conv3d.weight is {tuple(w.shape)}, expected {(cout, cin, *k)}")
-    scale = sd[name + ".bn.weight"].detach().double() / torch.sqrt(sd[name + ".bn.running_var"].detach().double() + bn_eps)
-    bias = sd[name + ".bn.bias"].detach().double() - sd[name + ".bn.running_mean"].detach().double() * scale
-    w = (w * scale.view(-1, 1, 1, 1, 1)).permute(0, 2, 3, 4, 1)                 # [cout][kt][kh][kw][cin]
-    ci, co = max(cin, cin_pad), max(cout, cout_pad)
-    full = torch.zeros((co, *k, ci), dtype=torch.float64, device=w.device)
-    full[:cout, ..., :cin] = w
-    kk = k[0] * k[1] * k[2] * ci
-    mat = torch.zeros((co, (kk + 3) // 4 * 4), dtype=torch.float32, device=w.device)
-    mat[:, :kk] = full.reshape(co, kk).float()
-    b = torch.zeros(co, dtype=torch.float32, device=w.device)
-    b[:cout] = bias.float()
-    return _Pk(w=mat, bias=b, taps=tuple(k), stride=tuple(s), cin=ci, cout=co)
+    scale, bias = f32net.bn_affine(*(sd[f"{name}.bn.{leaf}"] for leaf in ("weight", "bias", "running_mean", "running_var")), bn_eps)
+    return f32net.fold_conv(w, scale, bias, taps=k, stride=s, cin_pad=cin_pad, cout_pad=cout_pad)
 
 
-def _stack(layers: Sequence[_Pk]) -> _Pk:
-    """1 x 1 x 1 convolutions on the same input as ONE launch: weight rows and biases one after the other"""
-    a = layers[0]
-    assert all(l.taps == ONE and l.cin == a.cin and l.w.shape[1] == a.w.shape[1] for l in layers)
-    return _Pk(w=torch.cat([l.w for l in layers]), bias=torch.cat([l.bias for l in layers]), taps=a.taps, stride=a.stride, cin=a.cin,
-               cout=sum(l.cout for l in layers))
+_stack = f32net.stack_1x1
 
 
 def fold_network(sd, bn_eps: float = BN_EPS) -> _Pk:
@@ -153,20 +137,12 @@ def fold_network(sd, bn_eps: float = BN_EPS) -> _Pk:
 
 
 # ---- the network as a sequence of launches; `be` supplies conv / pool / mean / linear (the device library; torch ops in the CPU test) --
-class _Hip:
-    empty = staticmethod(lambda shape, like: torch.empty(shape, dtype=torch.float32, device=like.device))
-
+class _Hip(f32net._HipBase):
     @staticmethod
     def conv(x, layer, out=None):
         return ops.conv3d_same_f32(x, layer.w, layer.taps, layer.stride, out=out, bias=layer.bias, relu=True)
 
     pool = staticmethod(ops.maxpool3d_same_f32)
-    mean = staticmethod(ops.mean_rows_f32)
-
-    @staticmethod
-    def linear(x, w, b):
-        m = x.shape[0]
-        return ops.convnd_f32(x.view(m, 1, 1, 1, -1), w, ONE, ONE, (0, 0, 0), bias=b).view(m, -1)
 
 
 def _run_block(b: _Pk, x: torch.Tensor, be) -> torch.Tensor:
@@ -218,7 +194,7 @@ def run_network(pk: _Pk, x: torch.Tensor, be=_Hip, stages: Optional[dict] = None
 
 
 # ---- the module -------------------------------------------------------------------------------------------------------------------------
-class InceptionI3d(nn.Module):
+class InceptionI3d(f32net.F32Net):
     """pytorch_i3d.py:137-326 as a parameter holder.  Parameters are created uninitialised: load a state dict.  `bn_eps` is the
     epsilon of every BatchNorm (the reference's module: 1e-5)."""
 
@@ -236,84 +212,11 @@ class InceptionI3d(nn.Module):
         if in_channels != 3:
             raise NotImplementedError("only in_channels=3 is built: the stem reads the RGB output of preprocess_videos")
         self.num_classes, self.bn_eps, self.name = int(num_classes), float(bn_eps), name
-        for key, shape in state_dict_shapes(self.num_classes, in_channels).items():
-            mod, parts = self, key.split(".")
-            for p in parts[:-1]:
-                if p not in mod._modules:
-                    mod.add_module(p, nn.Module())
-                mod = mod._modules[p]
-            if parts[-1] == "num_batches_tracked":
-                mod.register_buffer(parts[-1], torch.zeros(shape, dtype=torch.int64))
-            elif parts[-1] in ("running_mean", "running_var"):
-                mod.register_buffer(parts[-1], torch.empty(shape, dtype=torch.float32))
-            else:
-                mod.register_parameter(parts[-1], nn.Parameter(torch.empty(shape, dtype=torch.float32), requires_grad=False))
-        self._packed: Optional[_Pk] = None
-        self._epoch = 0
-        self.requires_grad_(False)
+        f32net.declare(self, state_dict_shapes(self.num_classes, in_channels))
         self.eval()
 
-    @property
-    def device(self) -> torch.device:
-        return next(self.parameters()).device
-
-    def to(self, *args, **kw):
-        """moves to a device; dtype=torch.float32 is accepted, any other dtype refused: the metric computes in f32 only"""
-        device, dtype = kw.get("device"), kw.get("dtype")
-        for a in args:
-            if isinstance(a, torch.dtype):
-                dtype = a
-            elif isinstance(a, (str, torch.device, int)):
-                device = a
-        if dtype not in (None, torch.float32):
-            raise ValueError(f"InceptionI3d computes in float32 only, got dtype={dtype}")
-        if device is not None:
-            super().to(device)
-        return self
-
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        self._epoch += 1
-        return r
-
-    def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        own = super().state_dict()
-        missing = [k for k in own if k not in state_dict and not k.endswith("num_batches_tracked")]
-        if missing:
-            raise KeyError(f"InceptionI3d.load_state_dict: the checkpoint lacks {len(missing)} tensors, e.g. {missing[:3]}")
-        unexpected = [k for k in state_dict if k not in own]
-        if strict and unexpected:
-            raise KeyError(f"InceptionI3d.load_state_dict: {len(unexpected)} unexpected tensors, e.g. {unexpected[:3]}")
-        for k, p in own.items():
-            if k in state_dict and tuple(state_dict[k].shape) != tuple(p.shape):
-                raise ValueError(f"InceptionI3d.load_state_dict: {k!r} is {tuple(state_dict[k].shape)}, expected {tuple(p.shape)}")
-        r = super().load_state_dict({k: state_dict[k].to(own[k].dtype) if k in state_dict else own[k] for k in own}, strict=True)
-        self._epoch += 1
-        return r
-
-    def pack(self, device=None) -> _Pk:
-        """state_dict -> folded f32 kernel layouts inside ONE device blob built by weights.Blob and stamped with the shared pack key;
-        cached, repacked after load_state_dict / .to()"""
-        device = pack_device(device)
-        pk = self._packed
-        if pk is not None and pk.epoch == self._epoch and (device is None or pk.blob.device == device):
-            return pk
-        device = pack_device(device, self.device, ops, "InceptionI3d.pack")
-        blob = Blob()
-
-        def reg(o):
-            if isinstance(o, _Pk):
-                for k, v in list(o.__dict__.items()):
-                    o.__dict__[k] = blob.reg(v) if isinstance(v, torch.Tensor) else reg(v)
-            elif isinstance(o, list):
-                for v in o:
-                    reg(v)
-            return o
-
-        root = blob.finish(reg(fold_network(super().state_dict(), self.bn_eps)), device)
-        root.epoch = self._epoch
-        self._packed = root
-        return root
+    def _fold(self, state_dict) -> _Pk:
+        return fold_network(state_dict, self.bn_eps)
 
     @torch.no_grad()
     def forward(self, x: torch.Tensor, timesteps=None, rescale: bool = False, resize: bool = False, return_features: bool = True,
@@ -346,16 +249,11 @@ def load_i3d_pretrained(device: Union[str, torch.device] = "cpu",
     `bn_eps`: the reference's module says 1e-5 (pytorch_i3d.py:71), and that is the default for a plain checkpoint or a state dict.  The
     TensorFlow network the archive was converted from most likely used 1e-3, so a TorchScript archive defaults to 1e-3.  That choice
     is UNVERIFIED — no archive was available — as are the archive's key names; pass bn_eps to override."""
-    if weights is None:
-        weights = os.environ.get(ENV_WEIGHTS) or None
-    if weights is None:
-        raise FileNotFoundError("no I3D detector: pass weights=<path of i3d_torchscript.pt or of a checkpoint, or a state dict> or set the "
-                                f"environment variable {ENV_WEIGHTS}; nothing is downloaded here")
+    weights = f32net.resolve_checkpoint(weights, ENV_WEIGHTS, "I3D detector",
+                                        "path of i3d_torchscript.pt or of a checkpoint, or a state dict")
     archive = False
     if not isinstance(weights, dict):
-        path = os.fspath(weights)
-        if not os.path.isfile(path):
-            raise FileNotFoundError(f"I3D detector {path!r} (weights= or ${ENV_WEIGHTS}) does not exist")
+        path = weights
         import zipfile
 
         archive = zipfile.is_zipfile(path) and any(n.endswith("constants.pkl") or "/code/" in n for n in zipfile.ZipFile(path).namelist())

@@ -33,10 +33,9 @@ from __future__ import annotations
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
-import torch.nn as nn
 
-from . import ops
-from .weights import Blob, _Pk, pack_device
+from . import f32net, ops
+from .weights import _Pk
 
 DEFAULT_CHECKPOINT = ".checkpoints/imagebind_huge.pth"
 EPS = 1e-6                  # every LayerNorm of the three trunks and heads
@@ -119,7 +118,7 @@ def state_dict_shapes(config: Dict[str, Dict[str, int]]) -> Dict[str, List[int]]
     return {key: shape for tower in TOWERS if tower in config for key, shape in tower_keys(tower, config[tower]).values()}
 
 
-class CLIPModel(nn.Module):
+class CLIPModel(f32net.F32Net):
     """avgen/evaluations/models/clip.py:23-80 on the device library.  `config` maps tower name -> geometry (DEFAULT_CONFIG: ImageBind-Huge);
     a tower that `config` leaves out is not built, and its `encode_*` raises.  Parameters are created uninitialised: load a state dict."""
 
@@ -129,17 +128,8 @@ class CLIPModel(nn.Module):
         self._config = {t: dict(config[t]) for t in TOWERS if t in config}
         for t, cfg in self._config.items():
             self._check(t, cfg)
-            for key, shape in tower_keys(t, cfg).values():
-                mod, parts = self, key.split(".")
-                for p in parts[:-1]:
-                    if p not in mod._modules:
-                        mod.add_module(p, nn.Module())
-                    mod = mod._modules[p]
-                mod.register_parameter(parts[-1], nn.Parameter(torch.empty(shape, dtype=torch.float32), requires_grad=False))
+            f32net.declare(self, dict(tower_keys(t, cfg).values()))
         self.tokenizer = tokenizer
-        self._packed: Optional[_Pk] = None
-        self._epoch = 0
-        self.requires_grad_(False)
         self.eval()
 
     @staticmethod
@@ -160,63 +150,18 @@ class CLIPModel(nn.Module):
     def config(self) -> Dict[str, Dict[str, int]]:
         return {t: dict(c) for t, c in self._config.items()}
 
-    @property
-    def device(self) -> torch.device:
-        return next(self.parameters()).device
-
-    @property
-    def dtype(self) -> torch.dtype:
-        return torch.float32
-
-    def to(self, *args, **kw):
-        """moves to a device; dtype=torch.float32 is accepted, any other dtype refused: the metric computes in f32 only"""
-        device, dtype = kw.get("device"), kw.get("dtype")
-        for a in args:
-            if isinstance(a, torch.dtype):
-                dtype = a
-            elif isinstance(a, (str, torch.device, int)):
-                device = a
-        if dtype not in (None, torch.float32):
-            raise ValueError(f"CLIPModel computes in float32 only, got dtype={dtype}")
-        if device is not None:
-            super().to(device)
-        return self
-
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        self._epoch += 1
-        return r
-
-    def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        """ImageBind's checkpoint (the state dict of the whole multi-modal model; other modalities are ignored) or any subset that holds
-        every tensor of the towers this model was built with; a missing tensor raises KeyError naming it"""
-        own = super().state_dict()
-        missing = [k for k in own if k not in state_dict]
-        if missing:
-            raise KeyError(f"CLIPModel.load_state_dict: the checkpoint lacks {len(missing)} tensors, e.g. {missing[:3]}")
-        for k, p in own.items():
-            if tuple(state_dict[k].shape) != tuple(p.shape):
-                raise ValueError(f"CLIPModel.load_state_dict: {k!r} is {tuple(state_dict[k].shape)}, expected {tuple(p.shape)}")
-        r = super().load_state_dict({k: state_dict[k].to(torch.float32) for k in own}, strict=True)
-        self._epoch += 1
-        return r
+    # ImageBind's checkpoint is the state dict of the whole multi-modal model: the tensors of other modalities are ignored, and any
+    # subset will do that holds every tensor of the towers this model was built with (a missing one raises KeyError naming it)
+    STRICT_KEYS = False
 
     # ---- packing ------------------------------------------------------------------------------------------------------------------
-    def pack(self, device=None) -> _Pk:
-        """state_dict -> kernel layouts (stem weights tap-major and channels-last, the vision stem folded over time, cls / pos / bias_kv
-        flattened) inside ONE f32 device blob built by weights.Blob and stamped with the shared pack key; cached, repacked after
-        load_state_dict / .to().  Every item is f32, so the contents do not depend on the storage mode."""
-        device = pack_device(device)
-        pk = self._packed
-        if pk is not None and pk.epoch == self._epoch and (device is None or pk.blob.device == device):
-            return pk
-        device = pack_device(device, self.device, ops, "CLIPModel.pack")
-        sd = super().state_dict()
-        blob = Blob()
+    def _fold(self, sd) -> _Pk:
+        """kernel layouts: stem weights tap-major and channels-last, the vision stem folded over time, cls / pos / bias_kv flattened.
+        Every item is f32, so the contents do not depend on the storage mode."""
         root = _Pk()
         for tower, cfg in self._config.items():
             c = cfg["width"]
-            t = _Pk(blocks=[_Pk() for _ in range(cfg["layers"])])
+            t = _Pk()
             for name, (key, _) in tower_keys(tower, cfg).items():
                 w = sd[key].detach().to(torch.float32)
                 if name == "stem_w":
@@ -228,17 +173,18 @@ class CLIPModel(nn.Module):
                 holder, leaf = t, name
                 if name.startswith("blocks."):
                     _, i, leaf = name.split(".")
+                    if not hasattr(t, "blocks"):                                     # created where the table has the blocks: the
+                        t.blocks = [_Pk() for _ in range(cfg["layers"])]             # blob's items follow the order of the table
                     holder = t.blocks[int(i)]
-                setattr(holder, leaf, blob.reg(w))
+                setattr(holder, leaf, w)
             setattr(root, tower, t)
-        root = blob.finish(root, device)
+        return root
+
+    def _after_pack(self, root: _Pk) -> None:
         for t in self._config:                                                       # bias_k | bias_v as one row of 2 C values
             for blk in getattr(root, t).blocks:
                 if hasattr(blk, "bias_k"):
                     blk.bias_kv = torch.cat([blk.bias_k, blk.bias_v])
-        root.epoch = self._epoch
-        self._packed = root
-        return root
 
     def _tower(self, name: str, device) -> Tuple[Dict[str, int], _Pk]:
         if name not in self._config:
@@ -246,11 +192,7 @@ class CLIPModel(nn.Module):
         return self._config[name], getattr(self.pack(device), name)
 
     # ---- forward ------------------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], res: Optional[torch.Tensor] = None) -> torch.Tensor:
-        m = x.shape[0]
-        r = None if res is None else res.view(m, 1, 1, 1, -1)
-        return ops.convnd_f32(x.view(m, 1, 1, 1, -1), w, (1, 1, 1), (1, 1, 1), (0, 0, 0), bias=b, res=r).view(m, -1)
+    _linear = staticmethod(ops.linear_f32)
 
     def _blocks(self, h: torch.Tensor, blocks: Sequence[_Pk], b: int, seq: int, heads: int, causal: bool = False) -> torch.Tensor:
         """pre-LN blocks on h [b * seq, C]; a block with a bias_kv pair overwrites the key / value slots of each sequence's LAST row

@@ -1518,6 +1518,13 @@ def convnd_f32(x: torch.Tensor, w: torch.Tensor, taps, stride, pad, *, bias: Opt
     return out
 
 
+def linear_f32(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [m, K], w [N, ldw >= K] -> x @ w[:, :K].T + b + res, [m, N]: convnd_f32 with a (1, 1, 1) window over m images of 1 x 1 x 1"""
+    m = x.shape[0]
+    r = None if res is None else res.view(m, 1, 1, 1, -1)
+    return convnd_f32(x.view(m, 1, 1, 1, -1), w, (1, 1, 1), (1, 1, 1), (0, 0, 0), bias=b, res=r).view(m, -1)
+
+
 def maxpool_hw_f32(x: torch.Tensor) -> torch.Tensor:
     """[n, t, h, w, c] -> [n, t, ho, wo, c]: (1, 3, 3) window, stride (1, 2, 2), padding (0, 1, 1)"""
     _req(x, F32, "x")

@@ -271,11 +271,7 @@ class CLIPTextModel(nn.Module):
             return ids.argmax(dim=-1)
         return (ids == self._config["eos_token_id"]).int().argmax(dim=-1)
 
-    @staticmethod
-    def _linear(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, res: Optional[torch.Tensor] = None) -> torch.Tensor:
-        m = x.shape[0]
-        r = None if res is None else res.view(m, 1, 1, 1, -1)
-        return ops.convnd_f32(x.view(m, 1, 1, 1, -1), w, (1, 1, 1), (1, 1, 1), (0, 0, 0), bias=b, res=r).view(m, -1)
+    _linear = staticmethod(ops.linear_f32)
 
     def encode_ids(self, ids: torch.Tensor, b: int, seq: int, pk: Optional[_Pk] = None) -> torch.Tensor:
         """the launches alone: ids int32 [b * seq] on the device, already checked -> [b * seq, C] after final_layer_norm"""

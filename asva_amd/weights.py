@@ -172,6 +172,16 @@ class Blob:
         self.items.append(t.contiguous())
         return _Ref(len(self.items) - 1)
 
+    def reg_tree(self, root):
+        """`reg` for every tensor in a tree of attribute bags and lists, in attribute order (the order of the blob's items); -> root"""
+        if isinstance(root, _Pk):
+            for k, v in list(root.__dict__.items()):
+                root.__dict__[k] = self.reg(v) if isinstance(v, torch.Tensor) else self.reg_tree(v)
+        elif isinstance(root, list):
+            for v in root:
+                self.reg_tree(v)
+        return root
+
     def finish(self, root: _Pk, device, meta: bool = False) -> _Pk:
         """lays all items out in one blob on `device`, replaces the placeholders inside `root` by typed views of it and stamps
         `root` with the blob and the precision.pack_key() it was packed under"""

@@ -1,6 +1,7 @@
 """Records the layout of the packed weight blobs (tests/golden/pack_layout.json) — what the multi-GPU start-up broadcasts and the
-launch-plan export ships as CONST regions — for the tiny UNet and a small VAE in the four storage modes, on CPU through the
-tests/emu_ops.py seam.  tests/test_host_cpu.py::test_packed_blob_layout_is_pinned compares against the recorded file with the
+launch-plan export ships as CONST regions — for the tiny UNet and a small VAE in the four storage modes, and for the four f32 metric
+networks (FID's Inception-v3, FVD's I3D, the AVSync classifier, a small three-tower CLIPSim model) in the bf16 and split modes (they
+are f32 throughout: only the twin allocation of split precision changes their blob), on CPU through the tests/emu_ops.py seam.  tests/test_host_cpu.py::test_packed_blob_layout_is_pinned compares against the recorded file with the
 functions below; the file is regenerated only by a change that MEANS to move the layout.
 
     python oracle/gen_pack_layout.py             # print the records
@@ -23,7 +24,15 @@ if ROOT not in sys.path:
 FIXTURE = os.path.join(ROOT, "tests", "golden", "pack_layout.json")
 MODES = ("bf16", "fp16", "split", "plan")
 MODELS = ("unet", "vae")
-_NOT_LAYOUT = ("blob", "key", "split", "act_dtype", "plan", "subpixel")      # the blob itself and what pack() keys its cache on
+F32_MODELS = ("fid", "fvd", "avsync", "clipsim")        # f32 in every storage mode
+F32_MODES = ("bf16", "split")
+SEED = 0
+_NOT_LAYOUT = ("blob", "key", "split", "act_dtype", "plan", "subpixel", "epoch", "versions")      # the blob itself and what pack() keys its cache on
+_NOT_IN_BLOB = ("bias_kv",)     # CLIPModel joins bias_k | bias_v (two 256-byte-aligned items) into one row AFTER the blob is laid out
+
+
+def modes_of(which):
+    return F32_MODES if which in F32_MODELS else MODES
 
 
 def set_mode(mode):
@@ -41,6 +50,8 @@ def build_model(which):
     from tests.helpers import filled_unet, load_golden
 
     torch.manual_seed(0)
+    if which in F32_MODELS:
+        return build_f32_model(which)
     if which == "unet":         # its upsamplers keep the padded 3x3 form
         return filled_unet(load_golden("unet_tiny_e2e.pt")["config"])
     from asva_amd.vae import AutoencoderKL
@@ -48,18 +59,50 @@ def build_model(which):
     return AutoencoderKL(block_out_channels=(64, 128), layers_per_block=1, norm_num_groups=32)      # its upsampler takes the sub-pixel form
 
 
+def build_f32_model(which):
+    """the metric networks with seeded state dicts (the draws of the tests' restatements)"""
+    if which == "fid":
+        from asva_amd import fid
+        from tests import inception_ref as R
+
+        net = fid.InceptionV3()
+        net.load_state_dict(R.draw_state_dict(fid.state_dict_shapes(), SEED))
+    elif which == "fvd":
+        from asva_amd import fvd
+        from tests import i3d_ref as R
+
+        net = fvd.InceptionI3d()
+        net.load_state_dict(R.draw_state_dict(fvd.state_dict_shapes(), SEED))
+    elif which == "avsync":
+        from asva_amd import avsync as A
+        from tests import avsync_ref as R
+        from tests.helpers import load_shapes
+
+        net = A.AVSyncClassifier(A.AudioConv2DNet(), A.VideoR2Plus1DNet(), A.FCHead()).eval()
+        net.load_state_dict(R.draw_state_dict(load_shapes("avsync_state_dict_shapes.json"), SEED))
+    else:
+        from asva_amd.imagebind_eval import CLIPModel
+        from tests import imagebind_ref as R
+
+        net = CLIPModel(R.CONFIGS["tiny"])
+        net.load_state_dict(R.draw_state_dict(R.CONFIGS["tiny"]))
+    return net
+
+
 def pack_cpu(model):
     """model.pack("cpu") with the kernels' module replaced by its CPU emulation (no kernel runs while packing)"""
     from asva_amd import unet as U
     from asva_amd import vae as V
+    from asva_amd import ops
     from tests import emu_ops
 
-    old = U.ops, V.ops
+    old = U.ops, V.ops, getattr(ops, "EMULATED", False)
     U.ops = V.ops = emu_ops
+    ops.EMULATED = True         # the f32 networks call the kernels' module itself: this lets their pack() target the CPU
     try:
         return model.pack("cpu")
     finally:
-        U.ops, V.ops = old
+        U.ops, V.ops, ops.EMULATED = old
 
 
 def views_of(pk):
@@ -78,7 +121,7 @@ def views_of(pk):
                 walk(v, f"{path}[{i}]")
         elif hasattr(obj, "__dict__"):
             for k, v in vars(obj).items():
-                if path or k not in _NOT_LAYOUT:
+                if k not in _NOT_IN_BLOB and (path or k not in _NOT_LAYOUT):
                     walk(v, f"{path}.{k}" if path else k)
 
     walk(pk, "")
@@ -100,11 +143,13 @@ def main():
     ap.add_argument("--write", action="store_true", help=f"store the records as {os.path.relpath(FIXTURE, ROOT)}")
     ap.add_argument("--bytes", action="store_true", help="also print the SHA-256 of each blob's bytes")
     a = ap.parse_args()
-    rec = {which: {} for which in MODELS}
+    rec = {which: {} for which in MODELS + F32_MODELS}
     try:
         for mode in MODES:
             set_mode(mode)
-            for which in MODELS:
+            for which in MODELS + F32_MODELS:
+                if mode not in modes_of(which):
+                    continue
                 pk = pack_cpu(build_model(which))
                 rec[which][mode] = layout_record(pk)
                 print(which, mode, json.dumps(rec[which][mode]), *(["bytes_sha256", bytes_sha256(pk)] if a.bytes else []), flush=True)

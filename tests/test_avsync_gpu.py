@@ -151,6 +151,24 @@ def test_convnd_f32_refuses_bad_arguments(build):
         ops.convnd_f32(x, w, (1, 3, 3), (1, 1, 1), (0, 1, 1), res=torch.zeros(1, 4, 8, 8, 32, device=DEV))
 
 
+def test_linear_f32_is_the_convnd_f32_call_it_wraps(build):
+    """ops.linear_f32 (the linear layers of the FID, FVD, CLIPSim and CLIP text networks): bit for bit the (1, 1, 1)-window convnd_f32
+    on m 1 x 1 x 1 images, without and with bias, and with a residual; and within the bound of test_convnd_f32_against_float64"""
+    from asva_amd import ops
+
+    m, k, n = 3, 20, 5
+    g = torch.Generator().manual_seed(5)
+    x, w, b, res = (torch.randn(s, generator=g).to(DEV) for s in ((m, k), (n, k), (n,), (m, n)))
+    one, zero = (1, 1, 1), (0, 0, 0)
+    for bias, r in ((None, None), (b, None), (b, res), (None, res)):
+        out = ops.linear_f32(x, w, bias, r)
+        direct = ops.convnd_f32(x.view(m, 1, 1, 1, k), w, one, one, zero, bias=bias, res=None if r is None else r.view(m, 1, 1, 1, n))
+        assert out.shape == (m, n) and out.dtype == torch.float32 and torch.equal(out, direct.view(m, n))
+        ref = x.double() @ w.double().t() + (0 if bias is None else bias.double()) + (0 if r is None else r.double())
+        assert R.rel_l2(out, ref) < 1e-6, (bias is not None, r is not None)
+    assert torch.equal(ops.linear_f32(x, w), ops.linear_f32(x, w, None, None))
+
+
 # ---- pooling, mean, preprocessing ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shape", [(2, 3, 16, 16, 64), (1, 2, 15, 9, 64), (1, 1, 1, 1, 8)])
 def test_maxpool_is_exact(build, shape):

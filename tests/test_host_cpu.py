@@ -591,16 +591,24 @@ def test_packed_blob_layout_is_pinned(mode):
     """The packed blob is what the multi-GPU start-up broadcasts (asva_amd.dist) and the launch-plan export ships as a CONST region
     (asva_amd.plan): its byte length and the (attribute path, dtype, shape, byte offset) of every view, for the tiny UNet (padded 3x3
     upsamplers) and a small VAE (sub-pixel upsampler), are recorded in tests/golden/pack_layout.json by oracle/gen_pack_layout.py, whose
-    tree walk and digest this test shares.  A change that needs a new recording to pass has moved the layout."""
+    tree walk and digest this test shares.  So are those of the four f32 metric networks (FID's Inception-v3 and FVD's I3D at full size, the
+    AVSync classifier, a small three-tower CLIPSim model) in the bf16 and split modes: they are f32 in every mode, and only the twin
+    allocation of split precision changes their blob.  A change that needs a new recording to pass has moved the layout."""
     from oracle import gen_pack_layout as G
 
     want = load_shapes("pack_layout.json")
+    assert sorted(want) == sorted(G.MODELS + G.F32_MODELS) and all(sorted(want[w]) == sorted(G.modes_of(w)) for w in want)
     try:
         G.set_mode(mode)
         for which in G.MODELS:
             pk = G.pack_cpu(G.build_model(which))
             assert [b.up.subpixel for b in pk.up if b.up is not None] == ([False] * 3 if which == "unet" else [True]), which
             assert G.layout_record(pk) == want[which][mode], which
+        for which in G.F32_MODELS:
+            if mode in G.modes_of(which):
+                pk = G.pack_cpu(G.build_model(which))
+                assert pk.blob.dtype == torch.uint8 and all(dt == "torch.float32" for _, dt, _, _ in G.views_of(pk)), which
+                assert G.layout_record(pk) == want[which][mode], which
     finally:
         G.set_mode(None)
 
