@@ -65,7 +65,7 @@ const Entry kEntries[] = {
     AVSD_PLAN_ENTRY(avsd_timestep_embedding), AVSD_PLAN_ENTRY(avsd_guided_step),         AVSD_PLAN_ENTRY(avsd_vae_postprocess),
     AVSD_PLAN_ENTRY(avsd_vae_postprocess_u8), AVSD_PLAN_ENTRY(avsd_kaldi_fbank),         AVSD_PLAN_ENTRY(avsd_patchify),
     AVSD_PLAN_ENTRY(avsd_vit_tokens),       AVSD_PLAN_ENTRY(avsd_copy),                  AVSD_PLAN_ENTRY(avsd_xattn_pack_kv),
-    AVSD_PLAN_ENTRY_DESC(avsd_qproj_attention, avsd_xattn_desc), AVSD_PLAN_ENTRY(avsd_ff_block),
+    AVSD_PLAN_ENTRY_DESC(avsd_qproj_attention, avsd_xattn_desc), AVSD_PLAN_ENTRY(avsd_ff_block), AVSD_PLAN_ENTRY(avsd_temporal_block),
     // split-precision ("x2") entry points
     AVSD_PLAN_ENTRY(avsd_linear_small_m_x2), AVSD_PLAN_ENTRY(avsd_groupnorm_stats_x2),   AVSD_PLAN_ENTRY(avsd_groupnorm_apply_x2),
     AVSD_PLAN_ENTRY(avsd_layernorm_x2),     AVSD_PLAN_ENTRY(avsd_attention_x2),          AVSD_PLAN_ENTRY(avsd_temporal_attention_x2),

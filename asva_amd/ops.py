@@ -1228,6 +1228,58 @@ def ff_block(h: torch.Tensor, stats: torch.Tensor, w1_frag: torch.Tensor, w1_col
     return out
 
 
+def temporal_block_supported(M: int, C: int, heads: int, frames: int) -> bool:
+    """q|k|v projection + temporal attention + output projection of a transformer block as one launch (avsd_temporal_block): where it
+    is built and measured faster than the launches it replaces"""
+    return not P.SPLIT and bool(_lib.lib().avsd_temporal_block_supported(M, C, heads, frames))
+
+
+def temporal_block(h: torch.Tensor, stats: torch.Tensor, wqkv_frag: torch.Tensor, qkv_colsum: torch.Tensor, qkv_bias: torch.Tensor,
+                   posw: torch.Tensor, wo_frag: torch.Tensor, bo: torch.Tensor, *, b: int, frames: int, hw: int, heads: int,
+                   eps: float = 1e-5, scale: Optional[float] = None, rowstats: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = attention(LN(h + pos) Wqkv'^T + b) Wo^T + bo + h over the frames of each pixel, in one launch (+ the LayerNorm row
+    statistics of out); see avsd_temporal_block (include/avsd.h).  wqkv_frag, qkv_colsum, qkv_bias and posw come in the regrouped
+    q|k|v column order (weights.group_qkv), both weights in MFMA-fragment order (weights.pack_frag); stats [M, C / 32, 2] (of h + pos)
+    or pre-folded [M, 1, 2]."""
+    if P.SPLIT:
+        raise ValueError("temporal_block: not built for split precision (use the separate kernels)")
+    _req(h, P.ACT, "h")
+    _req(stats, F32, "stats")
+    _req(wqkv_frag, P.ACT, "wqkv_frag")
+    _req(wo_frag, P.ACT, "wo_frag")
+    for t, nm in ((qkv_colsum, "qkv_colsum"), (qkv_bias, "qkv_bias"), (posw, "posw"), (bo, "bo")):
+        _req(t, F32, nm)
+    if h.dim() != 2 or h.shape[0] != b * frames * hw:
+        raise ValueError("temporal_block: h must be [b * frames * hw, C]")
+    M, Cc = h.shape
+    nq = 4 * ((3 * Cc // 4 + 31) // 32 * 32)
+    if (not wqkv_frag.is_contiguous() or not wo_frag.is_contiguous() or wqkv_frag.numel() != nq * Cc or wo_frag.numel() != Cc * Cc
+            or qkv_colsum.numel() != nq or qkv_bias.numel() != nq or tuple(posw.shape) != (frames, nq) or bo.numel() != Cc
+            or not (qkv_colsum.is_contiguous() and qkv_bias.is_contiguous() and posw.is_contiguous() and bo.is_contiguous())):
+        raise ValueError("temporal_block: wqkv_frag [nq / 32, C / 16, 64, 8] with qkv_colsum [nq], qkv_bias [nq], posw [frames, nq] "
+                         "(nq = the regrouped, padded q|k|v columns); wo_frag [C / 32, C / 16, 64, 8] with bo [C]")
+    if not stats.is_contiguous() or stats.dim() != 3 or stats.shape[0] != M or stats.shape[2] != 2:
+        raise ValueError("temporal_block: stats must be contiguous f32 [M, C / 32 or 1, 2]")
+    if rowstats is not None:
+        _req(rowstats, F32, "rowstats")
+        if not rowstats.is_contiguous() or tuple(rowstats.shape) != (M, Cc // 32, 2):
+            raise ValueError("temporal_block: rowstats must be contiguous f32 [M, C / 32, 2]")
+    if out is None:
+        out = torch.empty((M, Cc), dtype=P.ACT, device=h.device)
+    _req(out, P.ACT, "out")
+    if out.shape != (M, Cc):
+        raise ValueError("temporal_block: out must be [M, C]")
+    if scale is None:
+        scale = float(Cc // heads) ** -0.5
+    a_ = (_p(h), _ld(h), _p(stats), int(stats.shape[1]), float(eps), _p(wqkv_frag), _p(qkv_colsum), _p(qkv_bias), _p(posw), _p(wo_frag),
+          _p(bo), _p(out), _ld(out), _p(rowstats), b, frames, hw, Cc, heads, float(scale))
+    _timed("temporal_block", 8.0 * M * Cc * Cc + 4.0 * M * frames * Cc, _nbytes(h, out, rowstats) + 2.0 * (nq + Cc) * Cc,
+           (h, stats, wqkv_frag, qkv_colsum, qkv_bias, posw, wo_frag, bo, rowstats, out),
+           lambda: check(_lib.lib().avsd_temporal_block(*a_, _stream()), "avsd_temporal_block"))
+    return out
+
+
 def temporal_attention(qkv: torch.Tensor, *, b: int, frames: int, hw: int, heads: int,
                        scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _req(qkv, P.ACT, "qkv")

@@ -39,7 +39,7 @@ from . import precision as P
 CONST, INPUT, OUTPUT = 1, 2, 3
 MAGIC = b"AVSDPLN1"
 _NOT_RECORDED = {"avsd_abi_version", "avsd_precision", "avsd_last_error", "avsd_device_info", "avsd_sizeof_gemm_desc",
-                 "avsd_sizeof_xattn_desc", "avsd_cross_attention_block_supported", "avsd_qproj_attention_supported", "avsd_ff_block_supported", "avsd_groupnorm_nchunks",
+                 "avsd_sizeof_xattn_desc", "avsd_cross_attention_block_supported", "avsd_qproj_attention_supported", "avsd_ff_block_supported", "avsd_temporal_block_supported", "avsd_groupnorm_nchunks",
                  "avsd_groupnorm_scratch_floats", "avsd_groupnorm_fused_supported", "avsd_gemm_conv3r_supported", "avsd_gemm_conv3r2d_supported"}
 
 

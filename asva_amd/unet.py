@@ -24,7 +24,7 @@ from . import precision as P
 
 from . import ops
 from .conditioning import mask_to_key_index
-from .weights import Blob, _Pk, _Ref, from_act, pack_conv1x1, pack_device, pack_frag, pack_geglu, pack_linear, subpixel_ups, to_act, to_planes  # noqa: F401  (_Ref: re-exported)
+from .weights import Blob, _Pk, _Ref, from_act, group_qkv, pack_conv1x1, pack_device, pack_frag, pack_geglu, pack_linear, subpixel_ups, to_act, to_planes  # noqa: F401  (_Ref: re-exported)
 
 CONFIG_NAME = "config.json"
 SAFETENSORS_NAME = "diffusion_pytorch_model.safetensors"
@@ -52,6 +52,9 @@ _FUSE_QATTN = os.environ.get("AVSD_FUSE_QATTN", "1") != "0"
 # at 32 x 32 (C = 320): GEGLU projection + FF-out + proj_out of a transformer block as one launch (avsd_ff_block): g and h' stay on
 # the chip.  AVSD_FUSE_FF=0 runs the three launches, for A/B runs.
 _FUSE_FF = os.environ.get("AVSD_FUSE_FF", "1") != "0"
+# at 32 x 32 (C = 320, 12 frames): q|k|v projection + temporal attention + output projection of a transformer block as one launch
+# (avsd_temporal_block): qkv and o stay on the chip.  AVSD_FUSE_TATTN=0 runs the three launches, for A/B runs.
+_FUSE_TATTN = os.environ.get("AVSD_FUSE_TATTN", "1") != "0"
 # the GEGLU projection re-folds the K / 32 LayerNorm partials of its rows in each of its 20-80 column tiles (+8-10 us per launch): fold
 # them once in a tiny launch (avsd_ln_fold) and hand it one pair per row
 _LN_PREFOLD = True
@@ -423,6 +426,13 @@ class Packer(Blob):
                 # FF-out and proj_out in the same order for the one-launch block tail (csrc/ffblock.hip; ops.ff_block_supported)
                 p.w2_f = reg(pack_frag(self.items[p.ff2.w.idx]))
                 p.wp_f = reg(pack_frag(self.items[p.proj_out.w.idx]))
+        if p.dim == 320 and not P.SPLIT:
+            # the LayerNorm-folded q|k|v projection with its columns regrouped by pairs of heads, and the output projection, in fragment
+            # order for the one-launch temporal attention (csrc/tblock.hip; ops.temporal_block_supported).  By the MODE, as above
+            at = p.attn_temp
+            at.wqkv_f = reg(pack_frag(group_qkv(self.items[at.wqkv_ln.idx])))
+            at.sqkv_f, at.bqkv_f = reg(group_qkv(self.items[at.sqkv_ln.idx])), reg(group_qkv(self.items[at.bqkv_ln.idx]))
+            at.wo_f = reg(pack_frag(self.items[at.wo.idx]))
         if p.audio:
             p.norm_audio = self.aff(b.norm_audio)
             p.attn_audio = self.attn(b.attn_audio, False, b.norm_audio)
@@ -831,6 +841,8 @@ class AudioUNet3DConditionModel(nn.Module):
         # pos . W'^T of the LayerNorm-folded q|k|v projection of the temporal attention: with it, LayerNorm(h + pos) needs no kernel
         # (avsd_gemm_desc.ln_rowvec).  The same rounded W' the GEMM multiplies h with, so W'.h + W'.pos = W'.(h + pos) exactly.
         c.posw = None if P.SPLIT else ops.linear_small_m(c.pos, tp.attn_temp.wqkv_ln, None)
+        # ... and in the regrouped column order of the one-launch temporal attention (csrc/tblock.hip)
+        c.posw_f = group_qkv(c.posw.t()).t().contiguous() if c.posw is not None and hasattr(tp.attn_temp, "wqkv_f") else None
         AudioUNet3DConditionModel._xa_caches(c, tp, key_index, idx_frames if idx_frames is not None else frames, frames)
         return c
 
@@ -1171,13 +1183,23 @@ def _transformer(st, x: _Act, p, hw, heads, split: int = 1, rest=False) -> _Act:
     # with pos . W'^T added inside its LayerNorm epilogue (avsd_gemm_desc.stats_pos / ln_rowvec) — no LayerNorm launch, no (M, C) round trip
     fold_temp = fused and _FUSE_LN_TEMP and not P.SPLIT and getattr(c, "posw", None) is not None and hasattr(p.attn_temp, "wqkv_ln")
     h = cross(h, a2, p.norm2, getattr(c, "xa_text", None), fold_temp, text_attention, stats_pos=(c.pos, L, Fr) if fold_temp else None)
-    if fold_temp:
-        qkv = ops.gemm(h.lo, p.attn_temp.wqkv_ln, bias=p.attn_temp.bqkv_ln, ln=(stats[si], p.attn_temp.sqkv_ln, eps), ln_pos=(c.posw, L, Fr))
+    tb_ok = getattr(ops, "temporal_block_supported", None)
+    if (hasattr(p.attn_temp, "wqkv_f") and _FUSE_TATTN and fold_temp and getattr(c, "posw_f", None) is not None and not P.SPLIT
+            and not st.f32_stream and P.PLAN is None and tb_ok is not None and tb_ok(M, C, heads, Fr)):
+        # one launch for the projection, the attention and the output projection: qkv and o never leave the chip (csrc/tblock.hip)
+        at = p.attn_temp
+        s_in = stats[si]
+        si ^= 1
+        h = _Act(ops.temporal_block(h.lo, s_in, at.wqkv_f, at.sqkv_f, at.bqkv_f, c.posw_f, at.wo_f, at.bo, b=B, frames=Fr, hw=L,
+                                    heads=heads, eps=eps, rowstats=stats[si]))
     else:
-        nt = ops.layernorm(h.lo, p.norm_temp.g, p.norm_temp.b, pos=c.pos, hw=L, frames=Fr)
-        qkv = ops.gemm(nt, p.attn_temp.wqkv)
-    o = ops.temporal_attention(qkv, b=B, frames=Fr, hw=L, heads=heads)
-    h = stream(o, p.attn_temp.wo, p.attn_temp.bo, h)
+        if fold_temp:
+            qkv = ops.gemm(h.lo, p.attn_temp.wqkv_ln, bias=p.attn_temp.bqkv_ln, ln=(stats[si], p.attn_temp.sqkv_ln, eps), ln_pos=(c.posw, L, Fr))
+        else:
+            nt = ops.layernorm(h.lo, p.norm_temp.g, p.norm_temp.b, pos=c.pos, hw=L, frames=Fr)
+            qkv = ops.gemm(nt, p.attn_temp.wqkv)
+        o = ops.temporal_attention(qkv, b=B, frames=Fr, hw=L, heads=heads)
+        h = stream(o, p.attn_temp.wo, p.attn_temp.bo, h)
     # 5. GEGLU feed-forward, activation fused in the first GEMM's epilogue (:361-371)
     if fused:
         wf = getattr(p, "w1_ln_f", None)

@@ -138,6 +138,21 @@ def pack_frag(wp: torch.Tensor) -> torch.Tensor:
     return wp.reshape(N // 32, 32, K // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous().reshape(N // 32, K // 16, 64, 8)
 
 
+def group_qkv(t: torch.Tensor, heads: int = 8) -> torch.Tensor:
+    """rows [q | k | v] of a fused projection (dim 0 = 3 C: a weight [3 C, K], its column sums or bias [3 C]) regrouped for the
+    one-launch temporal attention (csrc/tblock.hip): 4 groups of heads / 4 heads, each [q | k | v] of its heads (3 C / 4 rows)
+    padded with zeros to the next multiple of 32 + 16 — at C = 320: 240 -> 256 rows, [1024, ...] in all"""
+    C = t.shape[0] // 3
+    assert t.shape[0] == 3 * C and heads % 4 == 0 and C % heads == 0
+    n = C // 4                                # rows of q (or k, or v) per group
+    pad = (3 * n + 31) // 32 * 32
+    out = torch.zeros((4, pad) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+    src = t.reshape(3, 4, n, *t.shape[1:])
+    for j in range(3):
+        out[:, j * n:(j + 1) * n] = src[j]
+    return out.reshape(4 * pad, *t.shape[1:])
+
+
 def pad_rows(w: torch.Tensor, mult: int = 4) -> torch.Tensor:
     n = w.shape[0]
     if n % mult == 0:

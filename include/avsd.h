@@ -266,6 +266,24 @@ int avsd_ff_block(const void* h, int ldh, const float* ln_stats, int ln_nblk, fl
                   const float* b1, const void* w2_frag, const float* b2, const void* wp_frag, const float* bp, const void* x, int ldx,
                   void* out, int ldo, int M, int C, void* stream);
 
+/* The temporal attention of a 320-channel transformer block as one launch (csrc/tblock.hip), in place of a GEMM, avsd_temporal_attention
+ * and a GEMM:
+ *     qkv = LayerNorm(h + pos[frame]) . Wqkv'^T + b   [M][3 C]   (AVSD_GEMM_LNFUSE with ln_rowvec = posw)
+ *     o   = softmax(q k^T . scale) v                  [M][C]     over the `frames` rows of a pixel, per head
+ *     out = o . Wo^T + bo + h                         [M][C]     (+ rowstats as AVSD_GEMM_ROWSTATS writes them, unless NULL)
+ * M = B frames hw, row (b frames + f) hw + pixel.  h, out: 16-bit rows with leading dimensions ldh, ldo (multiples of 8); ln_stats: the
+ * f32 [M][ln_nblk][2] row statistics of h + pos (ln_nblk = C / 32, or 1: pre-folded).  The q|k|v columns come regrouped: 4 groups of 2
+ * heads, each [q | k | v] of its heads = 240 columns padded with zeros to 256, so wqkv_frag is [32][C / 16][64][8] (AVSD_GEMM_W_FRAG
+ * order of the regrouped [1024][C] matrix), qkv_colsum and qkv_bias [1024] and posw [frames][1024] in the same order; wo_frag
+ * [C / 32][C / 16][64][8].  qkv and o are rounded to 16 bits as the three launches round them and every sum runs in their order:
+ * bit-identical to them on LDS-direct tiles with the unrotated K walk.  Built for C = 320, 8 heads, 12 frames in the one-pass
+ * libraries; anything else is AVSD_EINVAL and launches nothing.  avsd_temporal_block_supported() tells where it is built AND measured
+ * faster than the launches it replaces (a lower bound on M). */
+int avsd_temporal_block_supported(int M, int C, int heads, int frames);
+int avsd_temporal_block(const void* h, int ldh, const float* ln_stats, int ln_nblk, float ln_eps, const void* wqkv_frag,
+                        const float* qkv_colsum, const float* qkv_bias, const float* posw, const void* wo_frag, const float* bo,
+                        void* out, int ldo, float* rowstats, int B, int frames, int hw, int C, int heads, float scale, void* stream);
+
 /* out[M, N] (f32) = act_out( act_in(x[M, K] f32) . W[N, K]^T + bias ), M <= 16.
  * act: 0 none, 1 SiLU.  Time-embedding MLP and the per-ResBlock time_emb_proj
  * (audio_cond_unet_3d_condition.py:673-680, ff_spatio_temp_resnet_3d.py:170), and the
