@@ -88,6 +88,8 @@ const Entry kEntries[] = {
     AVSD_PLAN_ENTRY(avsd_cosine_rows_f32),   AVSD_PLAN_ENTRY(avsd_normalize_rows_f32),
     // sample-rate conversion (csrc/audio.hip)
     AVSD_PLAN_ENTRY(avsd_resample_sinc_f32),
+    // baseline JPEG encoder (csrc/jpeg.hip)
+    AVSD_PLAN_ENTRY(avsd_jpeg_quantize_u8), AVSD_PLAN_ENTRY(avsd_jpeg_pack_i16),
 };
 
 struct Reloc {

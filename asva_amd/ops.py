@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import os
 import ctypes as C
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 
@@ -1507,6 +1507,47 @@ def resample_sinc_f32(wave: torch.Tensor, taps: torch.Tensor, orig: int, new: in
                                             out.stride(0) if n_wav > 1 else max(out.stride(0), n_out), _stream()),
           "avsd_resample_sinc_f32")
     return out
+
+
+# ---- baseline JPEG encoder (csrc/jpeg.hip; host side in asva_amd/video_io.py) ------------------------------------------------
+JPEG_SLOT_BYTES = 212      # AVSD_JPEG_SLOT_BYTES: the longest code string of one block, in whole 32-bit words
+
+
+def jpeg_quantize(frames: torch.Tensor, qy: torch.Tensor, qc: torch.Tensor) -> torch.Tensor:
+    """frames uint8 (n, H, W, 3) -> quantised DCT coefficients int16 (n, H/8, W/8, 3, 64) of Y, Cb, Cr in zigzag order; qy / qc:
+    the 64 luminance / chrominance table entries in natural order as 16-bit integers on the device; see avsd_jpeg_quantize_u8."""
+    for name, t, dt in (("frames", frames, (torch.uint8,)), ("qy", qy, (torch.int16, torch.uint16)), ("qc", qc, (torch.int16, torch.uint16))):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"jpeg_quantize: {name} must be a device tensor (libavsd_hip.so has no host path)")
+        if t.dtype not in dt or not t.is_contiguous():
+            raise ValueError(f"jpeg_quantize: {name} must be contiguous {dt[0]}, got {t.dtype}")
+    if frames.dim() != 4 or frames.shape[-1] != 3 or frames.shape[0] == 0 or qy.numel() != 64 or qc.numel() != 64:
+        raise ValueError(f"jpeg_quantize: frames must be a non-empty (n, H, W, 3) and the tables 64 entries, got {tuple(frames.shape)}, "
+                         f"{qy.numel()}, {qc.numel()}")
+    n, H, W, _ = frames.shape
+    coef = torch.empty((n, H // 8, W // 8, 3, 64), dtype=torch.int16, device=frames.device)
+    check(_lib.lib().avsd_jpeg_quantize_u8(_p(frames), n, H, W, _p(qy), _p(qc), _p(coef), _stream()), "avsd_jpeg_quantize_u8")
+    return coef
+
+
+def jpeg_pack(coef: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """coef int16 (n, ..., 64) with 3 x MCUs blocks per frame (what jpeg_quantize returns, or (n, blocks, 64)) -> (stream, nbytes):
+    stream uint8 (n, blocks * 212), frame f's entropy-coded segment in stream[f, :nbytes[f]] (unstuffed, padded with 1-bits; the
+    bytes behind it are not written), nbytes int32 (n,); see avsd_jpeg_pack_i16."""
+    if not isinstance(coef, torch.Tensor) or not coef.is_cuda:
+        raise ValueError("jpeg_pack: coef must be a device tensor (libavsd_hip.so has no host path)")
+    if coef.dtype != torch.int16 or not coef.is_contiguous() or coef.dim() < 3 or coef.shape[-1] != 64 or coef.shape[0] == 0:
+        raise ValueError(f"jpeg_pack: coef must be a non-empty contiguous int16 (n, ..., 64), got {coef.dtype} {tuple(coef.shape)}")
+    n = coef.shape[0]
+    blocks = coef.numel() // (n * 64)
+    if blocks == 0 or blocks % 3:
+        raise ValueError(f"jpeg_pack: {blocks} blocks per frame is not 3 x a number of MCUs")
+    scratch = torch.empty((n * blocks * (JPEG_SLOT_BYTES + 8),), dtype=torch.uint8, device=coef.device)
+    stream = torch.empty((n, blocks * JPEG_SLOT_BYTES), dtype=torch.uint8, device=coef.device)
+    nbytes = torch.empty((n,), dtype=torch.int32, device=coef.device)
+    check(_lib.lib().avsd_jpeg_pack_i16(_p(coef), n, blocks, _p(scratch), scratch.numel(), _p(stream), stream.stride(0), _p(nbytes),
+                                        _stream()), "avsd_jpeg_pack_i16")
+    return stream, nbytes
 
 
 def patchify(x: torch.Tensor, kh: int, kw: int, stride: int) -> torch.Tensor:

@@ -215,8 +215,10 @@ class AudioCondAnimationPipeline:
                                                  do_audio, audio_guidance_scale, text_guidance_scale)
         if output_latents:
             return latents
-        if output_type == "uint8":          # (b, f, H, W, 3) uint8 CPU frames, converted on the device
-            frames = self.vae.decode_to_uint8_frames(latents).cpu()
+        if output_type in ("uint8", "uint8_device"):     # (b, f, H, W, 3) uint8 frames, converted on the device
+            frames = self.vae.decode_to_uint8_frames(latents)
+            if output_type == "uint8":                   # "uint8_device" leaves them there (for video_io.encode_jpeg_frames)
+                frames = frames.cpu()
             return {"videos": frames} if return_dict else frames
         b, c, f, h, w = latents.shape
         videos = self.decode_latents(latents.permute(0, 2, 1, 3, 4).reshape(b * f, c, h, w))
@@ -280,6 +282,8 @@ def write_video(filename, video_array, fps, audio_array=None, audio_fps=16000, a
         warnings.warn(f"torchvision.io is unavailable ({type(e).__name__}): writing Motion-JPEG {path} instead of {filename}; "
                       "tools that glob *.mp4 must read it with asva_amd.video_io.read_mjpeg_avi", RuntimeWarning, stacklevel=2)
         return write_mjpeg_avi(path, video_array, fps, audio_array, audio_fps)
+    if torch.is_tensor(video_array) and video_array.is_cuda:     # frames left on the device for the Motion-JPEG writer's encoder
+        video_array = video_array.cpu()
     tvio.write_video(filename=filename, video_array=video_array, fps=fps, audio_array=audio_array, audio_fps=audio_fps,
                      audio_codec=audio_codec)
     return filename
@@ -317,6 +321,11 @@ def generate_videos(pipeline, image_path: str = "", audio_path: str = "", video_
     # kernels' tile choice, and — when the image latents come from `images` rather than `image_latents` — the VAE posterior sample:
     # latent_dist.sample() draws for all clips of the group in one call from the global RNG, so clip k > 0 sees other draws.
     group = max(1, int(clips_per_forward if clips_per_forward is not None else os.environ.get("AVSD_CLIPS_PER_FORWARD", "1")))
+    # frames stay on the device only when files are written and video_io's JPEG encoder runs there: the writer then copies back
+    # entropy-coded streams instead of raw frames.  Returned videos are CPU tensors either way.
+    from .video_io import get_jpeg_encoder
+
+    frames_type = "uint8_device" if save_template and get_jpeg_encoder() == "device" else "uint8"
     for k0 in range(0, len(clips), group):
         chunk = clips[k0:k0 + group]
         generator.manual_seed(seed)                       # every clip restarts from the same seed (:433)
@@ -343,7 +352,7 @@ def generate_videos(pipeline, image_path: str = "", audio_path: str = "", video_
                        video_length=video_num_frame, height=image_size[0], width=image_size[1],
                        num_inference_steps=getattr(pipeline, "generation_steps", 50),     # the reference hard-codes 50 (:442)
                        audio_guidance_scale=audio_guidance_scale, text_guidance_scale=text_guidance_scale,
-                       generator=generator, return_dict=False, output_type="uint8", **kw)
+                       generator=generator, return_dict=False, output_type=frames_type, **kw)
         for j, clip in enumerate(chunk):
             video, k = out[j], k0 + j
             if save_template:

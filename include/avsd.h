@@ -643,6 +643,31 @@ int avsd_cosine_rows_f32(const float* x, const float* y, float* out, int m, int 
  * order of avsd_cosine_rows_f32: a row's result does not depend on m. */
 int avsd_normalize_rows_f32(const float* x, float* y, int m, int C, void* stream);
 
+/* ---- baseline JPEG encoder for the Motion-JPEG clip writer (csrc/jpeg.hip; asva_amd/video_io.py:encode_jpeg_frames) -------
+ * Baseline sequential DCT, 8-bit, three components, 4:4:4: one MCU is one Y, one Cb and one Cr block, MCUs in raster order,
+ * no restart markers, the Huffman tables of Annex K.3-K.6.  f32 and integer arithmetic only: both builds give the same bytes.
+ * Markers, FF byte stuffing and the container are the caller's (FF -> FF 00 over the entropy-coded bytes). */
+#define AVSD_JPEG_SLOT_BYTES 212  /* code string of one block: at most 20 + 63 * 26 bits, rounded up to whole 32-bit words */
+/* frames u8 [n][H][W][3] (R, G, B) -> coef i16 [n][H/8][W/8][3][64], the quantised coefficients of Y, Cb, Cr in zigzag order:
+ * JFIF full-range YCbCr (Y = .299 R + .587 G + .114 B, Cb = -.168735892 R - .331264108 G + .5 B + 128,
+ * Cr = .5 R - .418687589 G - .081312411 B + 128), level shift by -128, orthonormal 8 x 8 DCT-II in f32, IEEE division by the
+ * table entry, rounding half away from zero.  qy / qc: the luminance / chrominance quantisation tables, 64 u16 each on the
+ * device, in NATURAL order (row-major 8 x 8; a DQT segment carries them in zigzag order).  H and W must be multiples of 8,
+ * frames 8-byte aligned.  A block's coefficients do not depend on n or on its neighbours. */
+int avsd_jpeg_quantize_u8(const void* frames_u8, int n, int H, int W, const uint16_t* qy, const uint16_t* qc, int16_t* coef,
+                          void* stream);
+/* coef i16 [n][blocks_per_frame][64] as written above (blocks_per_frame = 3 x the MCUs of a frame, block b belongs to component
+ * b % 3) -> the entropy-coded segment of each frame at out_u8 + f * out_stride, unstuffed, the last byte padded with 1-bits,
+ * and its length in nbytes[f].  The DC predictor is per component and starts at 0 in every frame; runs above 15 emit ZRL; EOB
+ * is emitted unless coefficient 63 is non-zero; bits are written MSB first.  Baseline range is assumed (DC differences within
+ * +-2047, AC within +-1023; values outside are clamped).  out_stride: a multiple of 4, at least blocks_per_frame *
+ * AVSD_JPEG_SLOT_BYTES (the worst case); the entry point zeroes what it uses, bytes past nbytes[f] are not written.
+ * scratch: at least n * blocks_per_frame * (AVSD_JPEG_SLOT_BYTES + 8) bytes on the device.  Three launches: code strings per
+ * block, an exclusive scan of their bit lengths per frame, and the shift of every string to its bit offset; words shared by
+ * neighbouring blocks are joined with integer atomic OR, so the bytes are a pure function of the coefficients. */
+int avsd_jpeg_pack_i16(const int16_t* coef, int n, int blocks_per_frame, void* scratch, int64_t scratch_bytes, void* out_u8,
+                       int64_t out_stride, int32_t* nbytes, void* stream);
+
 /* ---- launch plans (a host without Python runs the path) ----------------------------------------------------
  * A plan is the sequence of calls to the entry points above that one operation of the reference issues — the UNet forward
  * of a denoising step (audio_cond_unet_3d_condition.py:598-798), the per-clip conditioning projections, the VAE decode
