@@ -169,6 +169,10 @@ SIGNATURES = {
     # baseline JPEG encoder (csrc/jpeg.hip): f32 and integers in both builds
     "avsd_jpeg_quantize_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "avsd_jpeg_pack_i16": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    # baseline JPEG decoder (csrc/jpeg.hip): integers in both builds
+    "avsd_jpeg_decode_scan": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                      c_void_p, c_void_p, c_void_p]),
+    "avsd_jpeg_idct_rgb_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     # launch plans (asva_amd/plan.py records them; any host replays them)
     "avsd_plan_bundle_load": (c_int, [C.c_char_p, C.POINTER(c_void_p)]),
     "avsd_plan_bundle_free": (None, [c_void_p]),

@@ -5,6 +5,10 @@
 //   avsd_jpeg_pack_i16      coefficients -> one entropy-coded stream per frame (unstuffed, last byte padded with 1-bits)
 // f32 and integer arithmetic only: the same instructions in both builds of the library, so the same bytes.  Headers, FF
 // byte stuffing and the container are the host's.
+// And the baseline JPEG decoder of the clip readers (asva_amd/video_io.py:decode_jpeg_frames), 4:4:4 and 4:2:0, integers only:
+//   avsd_jpeg_decode_scan   unstuffed entropy-coded scans -> coefficients i16 (subsequence-parallel Huffman decoding)
+//   avsd_jpeg_idct_rgb_u8   coefficients -> dequantise -> libjpeg's integer IDCT -> chroma upsampling -> RGB u8
+// Its contract is the bytes libjpeg-turbo (PIL) returns for the same stream.
 #include "avsd_common.h"
 
 namespace {
@@ -304,6 +308,407 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_place_blocks_kernel(const uin
   }
 }
 
+// ---- decoder, stage 1: entropy decoding ----------------------------------------------------------------------------------
+// One workgroup owns a frame from the first phase to the last; nothing is handed to another workgroup and nothing spins.
+// The scan is cut into subsequences of `S` bits, JD_THREADS of them (a chunk) at a time.  A decoder state is (bit position,
+// block inside the MCU, next zigzag index), packed into one word.  Per chunk:
+//   A  every lane decodes its subsequence from the assumed state (start, 0, 0) - lane 0 from the state the chunk before ended in,
+//      which is final - and records its exit state and the blocks it completed;
+//   B  a lane whose predecessor's exit differs from the entry it used decodes again from that exit, until no entry changes.
+//      Lane 0 never changes, so lane i is final after at most i rounds: the loop is bounded by the lane count, and at its fixed
+//      point every entry IS the predecessor's exit, i.e. the sequential decoder's state - whatever S is and however quickly
+//      the streams synchronised;
+//   C  an exclusive prefix sum of the block counts, then the one pass that stores: each symbol starts in exactly one
+//      subsequence, so exactly one lane writes each coefficient (the frame's coefficients were zeroed first).
+// After the last chunk: the pass / fail word, then D, the per-component prefix sum that turns DC differences into DC values.
+// Every loop is bounded without trusting the stream: a symbol takes at least one bit and the bit position only grows; a symbol
+// that would end behind the scan's last bit is not decoded; block indices are checked before every store.
+constexpr int JD_THREADS = 1024;                 // 16 waves: a 4:4:4 frame of 256 x 256 is one chunk (0.66 ms per clip; 1.07 at 256 lanes)
+constexpr int JD_TAB = AVSD_JPEG_HUFF_WORDS;      // one table: lut[256], limit[16], offset[16], vals[256 bytes]
+constexpr int JD_SET = AVSD_JPEG_HUFF_SET_WORDS;  // [component][DC, AC]
+
+__device__ __forceinline__ uint64_t jd_pack(int p, int b, int k) { return ((uint64_t)(uint32_t)p << 16) | ((uint64_t)b << 8) | (uint64_t)k; }
+
+// The bit reader of one lane: `buf` holds the `avail` bits behind bit position p, MSB first; a word is appended whenever fewer than
+// 32 are left, so a symbol (at most 16 + 15 bits) is always whole, and a lane loads each word of its subsequence once per pass.
+// Words behind index (nbits >> 5) + 1 are not read (the kernel has checked that the ones up to there are inside the buffer), and
+// bits behind the scan's end read as ones, whatever the padding holds.
+struct JdBits {
+  const uint32_t* __restrict__ words;
+  uint64_t buf;
+  int avail, next, last;                          // next: index of the word to append; last: the last index that may be read
+
+  __device__ __forceinline__ uint32_t word(int i) const { return i <= last ? __builtin_bswap32(words[i]) : 0xffffffffu; }
+  __device__ __forceinline__ void open(const uint32_t* __restrict__ w, int p, int nbits) {
+    words = w;
+    last = (nbits >> 5) + 1;
+    next = p >> 5;
+    const uint64_t both = ((uint64_t)word(next) << 32) | word(next + 1);
+    next += 2;
+    buf = both << (p & 31);
+    avail = 64 - (p & 31);
+  }
+  __device__ __forceinline__ uint32_t peek(int p, int nbits) {
+    if (avail < 32) {
+      buf |= (uint64_t)word(next++) << (32 - avail);
+      avail += 32;
+    }
+    uint32_t bits = (uint32_t)(buf >> 32);
+    const int left = nbits - p;
+    if (left < 32) bits |= left <= 0 ? 0xffffffffu : (0xffffffffu >> left);
+    return bits;
+  }
+  __device__ __forceinline__ void skip(int n) {   // n <= 31 <= avail
+    buf <<= n;
+    avail -= n;
+  }
+};
+
+// -> the symbol and its code length, or -1 (length 16) for a prefix no code of the table has
+__device__ __forceinline__ int jd_symbol(const uint32_t* t, uint32_t bits, int& len) {
+  const uint32_t e = t[bits >> 24];
+  if (e) {
+    len = (int)(e >> 8);
+    return (int)(e & 0xffu);
+  }
+  const uint32_t v = bits >> 16;
+  len = 16;
+#pragma unroll 1
+  for (int l = 9; l <= 16; ++l) {
+    if (v < t[256 + l - 1]) {
+      len = l;
+      const uint32_t idx = ((v >> (16 - l)) + t[272 + l - 1]) & 0xffu;
+      return (int)((t[288 + (idx >> 2)] >> ((idx & 3u) * 8u)) & 0xffu);
+    }
+  }
+  return -1;
+}
+
+// Decodes the symbols that start in [position of `state`, end).  WRITE: stores them, the block index counted from blk_base, and
+// collects the status bits; otherwise only the exit state and the number of completed blocks come out.
+template <bool WRITE>
+__device__ __forceinline__ uint64_t jd_span(const uint32_t* __restrict__ words, const uint32_t* tabs, int bpm, uint64_t state, int end, int nbits,
+                                            int& nblk, int16_t* __restrict__ coef, int blk_base, int blocks_per_frame, int& st) {
+  int p = (int)(state >> 16), b = (int)((state >> 8) & 0xffu), k = (int)(state & 0xffu);
+  nblk = 0;
+  JdBits rd;
+  rd.open(words, p, nbits);
+  while (p < end) {
+    const uint32_t bits = rd.peek(p, nbits);
+    const int comp = bpm == 3 ? b : (b < 4 ? 0 : b - 3);
+    int len;
+    const int sym = jd_symbol(tabs + (comp * 2 + (k ? 1 : 0)) * JD_TAB, bits, len);
+    const int size = sym < 0 ? 0 : (sym & 15);
+    if (p + len + size > nbits) break;            // would read past the scan's end: not decoded
+    if (sym < 0) {
+      if (WRITE) st |= AVSD_JPEG_BAD_CODE;
+      p += 1;
+      rd.skip(1);
+      continue;
+    }
+    const int raw = size ? (int)((bits << len) >> (32 - size)) : 0;
+    const int val = size && !(raw >> (size - 1)) ? raw - (1 << size) + 1 : raw;
+    p += len + size;
+    rd.skip(len + size);
+    int at = -1;
+    if (k == 0) {
+      at = 0;
+      k = 1;
+    } else if (size == 0) {
+      k = (sym >> 4) == 15 ? k + 16 : 64;         // ZRL, or end of block
+    } else {
+      k += sym >> 4;
+      if (k > 63) {
+        if (WRITE) st |= AVSD_JPEG_BAD_INDEX;
+      } else {
+        at = k;
+      }
+      ++k;
+    }
+    if (WRITE && at >= 0) {
+      const int blk = blk_base + nblk;
+      if (blk < blocks_per_frame) coef[(int64_t)blk * 64 + at] = (int16_t)val;
+      else st |= AVSD_JPEG_TOO_MANY;
+    }
+    if (k >= 64) {
+      k = 0;
+      b = b + 1 == bpm ? 0 : b + 1;
+      ++nblk;
+    }
+  }
+  return jd_pack(p, b, k);
+}
+
+// exclusive prefix sum of `v` over the workgroup and the total; two barriers
+__device__ __forceinline__ int jd_block_scan(int v, int* wave_sums, int& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int incl = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int up = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += up;
+  }
+  __syncthreads();                                // the sums of the call before have been read
+  if (lane == 63) wave_sums[wave] = incl;
+  __syncthreads();
+  int before = 0;
+  total = 0;
+#pragma unroll
+  for (int w = 0; w < JD_THREADS / 64; ++w) {
+    const int s = wave_sums[w];
+    if (w < wave) before += s;
+    total += s;
+  }
+  return before + incl - v;
+}
+
+__global__ __launch_bounds__(JD_THREADS) void jpeg_decode_scan_kernel(const uint32_t* __restrict__ scan, int64_t scan_bytes,
+                                                                      const int64_t* __restrict__ offsets, const int32_t* __restrict__ nbits_of,
+                                                                      const int32_t* __restrict__ table_index,
+                                                                      const uint32_t* __restrict__ tables, int n_tables, int blocks_per_frame,
+                                                                      int bpm, int S, int16_t* __restrict__ coef_all,
+                                                                      int32_t* __restrict__ status, int32_t* __restrict__ rounds) {
+  __shared__ uint32_t tabs[JD_SET];
+  __shared__ uint64_t exit_s[JD_THREADS];
+  __shared__ int wave_sums[JD_THREADS / 64];
+  __shared__ int dc_sums[3][JD_THREADS / 64];
+  __shared__ int st_s;
+  const int tid = threadIdx.x, frame = blockIdx.x;
+  int16_t* coef = coef_all + (int64_t)frame * blocks_per_frame * 64;
+  const int64_t off = offsets[frame];
+  const int nbits = nbits_of[frame], ti = table_index[frame];
+  // the words a decode may touch: up to the one behind the word of the last bit; all of them inside the buffer, or nothing runs
+  const bool ok = off >= 0 && (off & 3) == 0 && nbits >= 0 && nbits <= AVSD_JPEG_MAX_SCAN_BITS && off + ((int64_t)(nbits >> 5) + 2) * 4 <= scan_bytes &&
+                  ti >= 0 && ti < n_tables;
+  {
+    uint4* z = reinterpret_cast<uint4*>(coef);    // blocks_per_frame * 128 bytes, 16-byte aligned (checked by the entry point)
+    for (int i = tid; i < blocks_per_frame * 8; i += JD_THREADS) z[i] = make_uint4(0u, 0u, 0u, 0u);
+  }
+  if (tid == 0) st_s = 0;
+  if (!ok) {                                      // uniform over the workgroup
+    if (tid == 0) {
+      status[frame] = AVSD_JPEG_BAD_ARGS;
+      if (rounds) rounds[frame] = 0;
+    }
+    return;
+  }
+  for (int i = tid; i < JD_SET; i += JD_THREADS) tabs[i] = tables[(int64_t)ti * JD_SET + i];
+  __syncthreads();
+  const uint32_t* words = scan + (off >> 2);
+  const int nsub = (int)(((int64_t)nbits + S - 1) / S);
+  uint64_t carry = 0;                             // (0, 0, 0)
+  int carry_blocks = 0, max_rounds = 0, st = 0;
+  for (int c0 = 0; c0 < nsub; c0 += JD_THREADS) {
+    const int j = c0 + tid;
+    const bool live = j < nsub;
+    const int start = live ? j * S : 0;           // j * S < nbits < 2^31
+    const int end = live ? (int)min((int64_t)start + S, (int64_t)nbits) : 0;
+    uint64_t entry = tid == 0 ? carry : jd_pack(start, 0, 0);
+    int nblk = 0, unused = 0;
+    uint64_t out = entry;
+    if (live) out = jd_span<false>(words, tabs, bpm, entry, end, nbits, nblk, nullptr, 0, 0, unused);       // phase A
+    exit_s[tid] = out;
+    __syncthreads();
+    int r = 0;
+    for (; r < JD_THREADS; ++r) {                 // phase B
+      uint64_t pred = entry;
+      if (live && tid > 0) pred = exit_s[tid - 1];
+      const bool redo = pred != entry;
+      if (!__syncthreads_or(redo)) break;         // also: every lane has read its predecessor before any lane writes
+      if (redo) {
+        entry = pred;
+        out = jd_span<false>(words, tabs, bpm, entry, end, nbits, nblk, nullptr, 0, 0, unused);
+        exit_s[tid] = out;
+      }
+      __syncthreads();
+    }
+    max_rounds = max(max_rounds, r);
+    int total;
+    const int base = carry_blocks + jd_block_scan(live ? nblk : 0, wave_sums, total);                       // phase C
+    if (live) jd_span<true>(words, tabs, bpm, entry, end, nbits, nblk, coef, base, blocks_per_frame, st);
+    carry = exit_s[min(nsub - c0, JD_THREADS) - 1];
+    carry_blocks += total;                        // <= nbits
+    __syncthreads();                              // exit_s is rewritten by the next chunk
+  }
+  if (st) atomicOr(&st_s, st);
+  __syncthreads();                                // also makes this workgroup's coefficient stores visible to all its lanes
+  if (tid == 0) {
+    int s = st_s;
+    const int p = (int)(carry >> 16), left = nbits - p;
+    if (carry_blocks != blocks_per_frame || (carry & 0xffffu) != 0) s |= AVSD_JPEG_INCOMPLETE;
+    // the reader gives ones behind the end, so the bits that are left must make the top byte all ones
+    JdBits rd;
+    rd.open(words, p, nbits);
+    if (left >= 8 || (rd.peek(p, nbits) >> 24) != 0xffu) s |= AVSD_JPEG_BAD_TAIL;
+    status[frame] = s;
+    if (rounds) rounds[frame] = max_rounds;
+  }
+  // phase D: thread t owns a contiguous run of MCUs; sums of its DC differences per component, scanned over the workgroup
+  const int n_mcu = blocks_per_frame / bpm;
+  const int per = (n_mcu + JD_THREADS - 1) / JD_THREADS;
+  const int lo = min(tid * per, n_mcu), hi = min(lo + per, n_mcu);
+  int s0 = 0, s1 = 0, s2 = 0;                     // scalars, not an array: a component index would put it into scratch
+  for (int m = lo; m < hi; ++m)
+    for (int b = 0; b < bpm; ++b) {
+      const int c = bpm == 3 ? b : (b < 4 ? 0 : b - 3), d = coef[((int64_t)m * bpm + b) * 64];
+      s0 += c == 0 ? d : 0, s1 += c == 1 ? d : 0, s2 += c == 2 ? d : 0;
+    }
+  int total;
+  int p0 = jd_block_scan(s0, dc_sums[0], total), p1 = jd_block_scan(s1, dc_sums[1], total), p2 = jd_block_scan(s2, dc_sums[2], total);
+  for (int m = lo; m < hi; ++m)
+    for (int b = 0; b < bpm; ++b) {
+      const int c = bpm == 3 ? b : (b < 4 ? 0 : b - 3);
+      int16_t* dc = coef + ((int64_t)m * bpm + b) * 64;
+      const int d = *dc;
+      p0 += c == 0 ? d : 0, p1 += c == 1 ? d : 0, p2 += c == 2 ? d : 0;
+      *dc = (int16_t)(c == 0 ? p0 : c == 1 ? p1 : p2);
+    }
+}
+
+// ---- decoder, stage 2: dequantise, inverse DCT, upsample, colour ---------------------------------------------------------
+// jidctint.c ("islow": 13-bit constants, 2 extra bits after the first pass).  libjpeg-turbo runs this arithmetic in 16-bit
+// vector lanes: the inputs of a pass, i0 +- i4, z3 and z4 wrap to int16 and the results of a pass saturate to int16.  These are
+// no-ops for any stream made from pixels; they are kept so that streams built from extreme coefficients decode to the same bytes.
+__device__ __forceinline__ int jd_wrap16(int x) { return (int)(int16_t)x; }
+__device__ __forceinline__ int jd_sat16(int x) { return max(-32768, min(32767, x)); }
+template <int SHIFT>
+__device__ __forceinline__ void jd_idct8(const int (&i)[8], int (&o)[8]) {
+  int z1 = (i[2] + i[6]) * 4433;
+  const int t2 = z1 - i[6] * 15137, t3 = z1 + i[2] * 6270;
+  const int t0 = jd_wrap16(i[0] + i[4]) * 8192, t1 = jd_wrap16(i[0] - i[4]) * 8192;
+  const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+  int a0 = i[7], a1 = i[5], a2 = i[3], a3 = i[1];
+  z1 = a0 + a3;
+  int z2 = a1 + a2, z3 = jd_wrap16(a0 + a2), z4 = jd_wrap16(a1 + a3);
+  const int z5 = (z3 + z4) * 9633;
+  a0 *= 2446, a1 *= 16819, a2 *= 25172, a3 *= 12299;
+  z1 *= -7373, z2 *= -20995;
+  z3 = z3 * -16069 + z5, z4 = z4 * -3196 + z5;
+  a0 += z1 + z3, a1 += z2 + z4, a2 += z2 + z3, a3 += z1 + z4;
+  const int r = 1 << (SHIFT - 1);
+  o[0] = jd_sat16((t10 + a3 + r) >> SHIFT), o[7] = jd_sat16((t10 - a3 + r) >> SHIFT);
+  o[1] = jd_sat16((t11 + a2 + r) >> SHIFT), o[6] = jd_sat16((t11 - a2 + r) >> SHIFT);
+  o[2] = jd_sat16((t12 + a1 + r) >> SHIFT), o[5] = jd_sat16((t12 - a1 + r) >> SHIFT);
+  o[3] = jd_sat16((t13 + a0 + r) >> SHIFT), o[4] = jd_sat16((t13 - a0 + r) >> SHIFT);
+}
+
+constexpr int JI_THREADS = 256;                   // 32 blocks of coefficients, eight lanes each
+__device__ const unsigned char kNaturalOfZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                                       41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                                       30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// Eight lanes per block.  Lane (block, c): loads zigzag positions 8c .. 8c + 7 and stores their products with the table at
+// their natural places; then does column c; then row c, and stores its eight samples into the component's plane.  Planes of a
+// frame: Y [mcus_h * 8 v][mcus_w * 8 v], then Cb and Cr [mcus_h * 8][mcus_w * 8], v = 2 for 4:2:0: whole MCUs, so every row of
+// eight samples is 8-byte aligned.
+__global__ __launch_bounds__(JI_THREADS) void jpeg_idct_kernel(const int16_t* __restrict__ coef, const uint16_t* __restrict__ qtabs, int n_qsets,
+                                                               const int32_t* __restrict__ q_index, int blocks_per_frame, int bpm, int mcus_w,
+                                                               int mcus_h, int64_t n_blocks, unsigned char* __restrict__ planes) {
+  __shared__ int ws[32][72];                      // 72: in the column pass the 32 lanes of a half-wave fall on 32 banks
+  const int tid = threadIdx.x, bl = tid >> 3, c = tid & 7;
+  const int64_t blk = (int64_t)blockIdx.x * 32 + bl;
+  const bool live = blk < n_blocks;               // uniform over the eight lanes of a block
+  int frame = 0, in_frame = 0, comp = 0;
+  if (live) {
+    frame = (int)(blk / blocks_per_frame);
+    in_frame = (int)(blk - (int64_t)frame * blocks_per_frame);
+    const int b = in_frame % bpm;
+    comp = bpm == 3 ? b : (b < 4 ? 0 : b - 3);
+    int qi = q_index[frame];
+    if (qi < 0 || qi >= n_qsets) qi = 0;          // never from video_io; keeps the read inside the table
+    const uint4 raw = *reinterpret_cast<const uint4*>(coef + blk * 64 + c * 8);
+    const uint16_t* q = qtabs + ((int64_t)qi * 3 + comp) * 64 + c * 8;
+    const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int v = (int)(int16_t)(w[e >> 1] >> ((e & 1) * 16));
+      ws[bl][kNaturalOfZigzag[c * 8 + e]] = jd_wrap16(v * (int)q[e]);
+    }
+  }
+  __syncthreads();
+  int in[8], out[8];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) in[r] = live ? ws[bl][r * 8 + c] : 0;
+  // the vector code's shortcut: a block whose rows 1..7 are all zero becomes row 0 << 2 in 16 bits - the value of the full
+  // pass, except that it wraps where the full pass saturates
+  const bool col_flat = (in[1] | in[2] | in[3] | in[4] | in[5] | in[6] | in[7]) == 0;
+  const uint64_t flat = __ballot(col_flat);
+  const bool blk_flat = ((flat >> ((tid & 63) & ~7)) & 0xffull) == 0xffull;
+  if (blk_flat) {
+#pragma unroll
+    for (int r = 0; r < 8; ++r) out[r] = jd_wrap16(in[0] * 4);
+  } else {
+    jd_idct8<11>(in, out);
+  }
+  if (live) {
+#pragma unroll
+    for (int r = 0; r < 8; ++r) ws[bl][r * 8 + c] = out[r];          // own column only
+  }
+  __syncthreads();
+  if (!live) return;
+#pragma unroll
+  for (int x = 0; x < 8; ++x) in[x] = ws[bl][c * 8 + x];
+  jd_idct8<18>(in, out);
+  uint32_t lo = 0, hi = 0;
+#pragma unroll
+  for (int x = 0; x < 4; ++x) {
+    lo |= (uint32_t)max(0, min(255, out[x] + 128)) << (8 * x);
+    hi |= (uint32_t)max(0, min(255, out[x + 4] + 128)) << (8 * x);
+  }
+  const int v = bpm == 3 ? 1 : 2;
+  const int mcu = in_frame / bpm, b = in_frame - mcu * bpm;
+  const int my = mcu / mcus_w, mx = mcu - my * mcus_w;
+  const int64_t c_plane = (int64_t)mcus_h * mcus_w * 64, y_plane = c_plane * v * v;
+  unsigned char* base = planes + (int64_t)frame * (y_plane + 2 * c_plane);
+  int by = my, bx = mx, pw = mcus_w * 8;
+  if (comp == 0) {
+    pw *= v;
+    if (v == 2) by = 2 * my + (b >> 1), bx = 2 * mx + (b & 1);
+  } else {
+    base += y_plane + (comp - 1) * c_plane;
+  }
+  *reinterpret_cast<uint2*>(base + ((int64_t)by * 8 + c) * pw + bx * 8) = make_uint2(lo, hi);
+}
+
+// One lane per pixel.  4:2:0 chroma: libjpeg's "fancy" triangle filter over the ceil(H/2) x ceil(W/2) real samples, the edge
+// rows and columns repeated; then jdcolor.c's 16-bit fixed-point YCbCr -> RGB.
+__device__ __forceinline__ int jd_fancy(const unsigned char* __restrict__ p, int pw, int ch, int cw, int y, int x) {
+  const int r = y >> 1, j = x >> 1;
+  const int rn = (y & 1) ? min(r + 1, ch - 1) : max(r - 1, 0);
+  const int jn = (x & 1) ? min(j + 1, cw - 1) : max(j - 1, 0);
+  const int v = 3 * (int)p[(int64_t)r * pw + j] + (int)p[(int64_t)rn * pw + j];
+  const int vn = 3 * (int)p[(int64_t)r * pw + jn] + (int)p[(int64_t)rn * pw + jn];
+  return (3 * v + vn + ((x & 1) ? 7 : 8)) >> 4;
+}
+
+__global__ __launch_bounds__(256) void jpeg_colour_kernel(const unsigned char* __restrict__ planes, int H, int W, int v, int mcus_w, int mcus_h,
+                                                          int64_t n_pixels, unsigned char* __restrict__ frames) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_pixels) return;
+  const int64_t hw = (int64_t)H * W;
+  const int64_t frame = i / hw;
+  const int in_frame = (int)(i - frame * hw);     // H, W <= 65535 and H * W < 2^31 (checked by the entry point)
+  const int y = in_frame / W, x = in_frame - y * W;
+  const int64_t c_plane = (int64_t)mcus_h * mcus_w * 64, y_plane = c_plane * v * v;
+  const unsigned char* base = planes + frame * (y_plane + 2 * c_plane);
+  const int cpw = mcus_w * 8;
+  const int Y = base[(int64_t)y * (cpw * v) + x];
+  int cb, cr;
+  if (v == 1) {
+    cb = base[y_plane + (int64_t)y * cpw + x];
+    cr = base[y_plane + c_plane + (int64_t)y * cpw + x];
+  } else {
+    const int ch = (H + 1) >> 1, cw = (W + 1) >> 1;
+    cb = jd_fancy(base + y_plane, cpw, ch, cw, y, x);
+    cr = jd_fancy(base + y_plane + c_plane, cpw, ch, cw, y, x);
+  }
+  cb -= 128, cr -= 128;
+  unsigned char* o = frames + i * 3;
+  o[0] = (unsigned char)max(0, min(255, Y + ((91881 * cr + 32768) >> 16)));
+  o[1] = (unsigned char)max(0, min(255, Y + ((-22554 * cb - 46802 * cr + 32768) >> 16)));
+  o[2] = (unsigned char)max(0, min(255, Y + ((116130 * cb + 32768) >> 16)));
+}
+
 }  // namespace
 
 extern "C" int avsd_jpeg_quantize_u8(const void* frames_u8, int n, int H, int W, const uint16_t* qy, const uint16_t* qc, int16_t* coef,
@@ -353,5 +758,54 @@ extern "C" int avsd_jpeg_pack_i16(const int16_t* coef, int n, int blocks_per_fra
   hipLaunchKernelGGL(jpeg_place_blocks_kernel, dim3((unsigned)grid), dim3(JP_THREADS), 0, s, slots, bitlen, bitoff, blocks_per_frame, n_blocks,
                      out, out_stride / 4);
   AVSD_CHECK_LAUNCH("jpeg_pack place launch");
+  return AVSD_OK;
+}
+
+extern "C" int avsd_jpeg_decode_scan(const void* scan, int64_t scan_bytes, const int64_t* offsets, const int32_t* nbits, const int32_t* table_index,
+                                     const uint32_t* tables, int n_tables, int n, int blocks_per_frame, int sampling, int subseq_bits,
+                                     int16_t* coef, int32_t* status, int32_t* rounds, void* stream) {
+  AVSD_REQUIRE(scan && offsets && nbits && table_index && tables && coef && status, "jpeg_decode_scan: null pointer");
+  AVSD_REQUIRE(sampling == AVSD_JPEG_444 || sampling == AVSD_JPEG_420, "jpeg_decode_scan: sampling %d is neither AVSD_JPEG_444 nor AVSD_JPEG_420",
+               sampling);
+  const int bpm = sampling == AVSD_JPEG_444 ? 3 : 6;
+  AVSD_REQUIRE(n > 0 && n_tables > 0 && blocks_per_frame > 0 && blocks_per_frame % bpm == 0,
+               "jpeg_decode_scan: n (%d) and n_tables (%d) must be positive, blocks_per_frame (%d) a multiple of the %d blocks of an MCU", n,
+               n_tables, blocks_per_frame, bpm);
+  AVSD_REQUIRE(blocks_per_frame <= (1 << 22), "jpeg_decode_scan: %d blocks per frame exceed 2^22", blocks_per_frame);
+  AVSD_REQUIRE(subseq_bits >= 128 && subseq_bits <= 4096 && (subseq_bits & (subseq_bits - 1)) == 0,
+               "jpeg_decode_scan: subseq_bits (%d) must be a power of two in 128..4096", subseq_bits);
+  AVSD_REQUIRE(scan_bytes >= 8 && scan_bytes % 4 == 0, "jpeg_decode_scan: scan_bytes (%lld) must be a multiple of 4, at least 8", (long long)scan_bytes);
+  AVSD_REQUIRE((uintptr_t)scan % 4 == 0 && (uintptr_t)coef % 16 == 0 && (uintptr_t)tables % 4 == 0,
+               "jpeg_decode_scan: scan and tables need 4-byte, coefficients 16-byte alignment");
+  hipLaunchKernelGGL(jpeg_decode_scan_kernel, dim3((unsigned)n), dim3(JD_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
+                     static_cast<const uint32_t*>(scan), scan_bytes, offsets, nbits, table_index, tables, n_tables, blocks_per_frame, bpm, subseq_bits,
+                     coef, status, rounds);
+  AVSD_CHECK_LAUNCH("jpeg_decode_scan launch");
+  return AVSD_OK;
+}
+
+extern "C" int avsd_jpeg_idct_rgb_u8(const int16_t* coef, int n, int H, int W, int sampling, const uint16_t* qtabs, int n_qsets,
+                                     const int32_t* q_index, void* planes, int64_t planes_bytes, void* frames_u8, void* stream) {
+  AVSD_REQUIRE(coef && qtabs && q_index && planes && frames_u8, "jpeg_idct_rgb: null pointer");
+  AVSD_REQUIRE(sampling == AVSD_JPEG_444 || sampling == AVSD_JPEG_420, "jpeg_idct_rgb: sampling %d is neither AVSD_JPEG_444 nor AVSD_JPEG_420", sampling);
+  AVSD_REQUIRE(n > 0 && n_qsets > 0 && H > 0 && W > 0 && H <= 65535 && W <= 65535 && (int64_t)H * W < (1ll << 31),
+               "jpeg_idct_rgb: bad sizes (n %d, n_qsets %d, H %d, W %d)", n, n_qsets, H, W);
+  const int v = sampling == AVSD_JPEG_444 ? 1 : 2, bpm = v == 1 ? 3 : 6;
+  const int mcus_w = (W + 8 * v - 1) / (8 * v), mcus_h = (H + 8 * v - 1) / (8 * v);
+  const int64_t blocks_per_frame = (int64_t)mcus_w * mcus_h * bpm;
+  AVSD_REQUIRE(blocks_per_frame <= (1 << 22), "jpeg_idct_rgb: %lld blocks per frame exceed 2^22", (long long)blocks_per_frame);
+  const int64_t need = (int64_t)n * mcus_w * mcus_h * 64 * (v * v + 2);
+  AVSD_REQUIRE(planes_bytes >= need, "jpeg_idct_rgb: planes of %lld bytes, need %lld", (long long)planes_bytes, (long long)need);
+  AVSD_REQUIRE((uintptr_t)coef % 16 == 0 && (uintptr_t)planes % 8 == 0, "jpeg_idct_rgb: coefficients need 16-byte, planes 8-byte alignment");
+  const int64_t n_blocks = (int64_t)n * blocks_per_frame, n_pixels = (int64_t)n * H * W;
+  const int64_t grid1 = (n_blocks + 31) / 32, grid2 = (n_pixels + 255) / 256;
+  AVSD_REQUIRE(grid1 <= 0x7fffffffLL && grid2 <= 0x7fffffffLL, "jpeg_idct_rgb: %d frames of %d x %d exceed the grid", n, H, W);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)grid1), dim3(JI_THREADS), 0, s, coef, qtabs, n_qsets, q_index, (int)blocks_per_frame, bpm,
+                     mcus_w, mcus_h, n_blocks, static_cast<unsigned char*>(planes));
+  AVSD_CHECK_LAUNCH("jpeg_idct_rgb idct launch");
+  hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)grid2), dim3(256), 0, s, static_cast<const unsigned char*>(planes), H, W, v, mcus_w, mcus_h,
+                     n_pixels, static_cast<unsigned char*>(frames_u8));
+  AVSD_CHECK_LAUNCH("jpeg_idct_rgb colour launch");
   return AVSD_OK;
 }

@@ -90,6 +90,8 @@ const Entry kEntries[] = {
     AVSD_PLAN_ENTRY(avsd_resample_sinc_f32),
     // baseline JPEG encoder (csrc/jpeg.hip)
     AVSD_PLAN_ENTRY(avsd_jpeg_quantize_u8), AVSD_PLAN_ENTRY(avsd_jpeg_pack_i16),
+    // baseline JPEG decoder (csrc/jpeg.hip)
+    AVSD_PLAN_ENTRY(avsd_jpeg_decode_scan), AVSD_PLAN_ENTRY(avsd_jpeg_idct_rgb_u8),
 };
 
 struct Reloc {

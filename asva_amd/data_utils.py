@@ -15,7 +15,9 @@ numpy only, so
     waveforms;
   * video files: torchvision's VideoReader when importable; additionally a pre-decoded clip container
     (`.npz` with `frames` uint8 (T, H, W, 3), `fps`, optional `audio` f32 (C, T) + `audio_sr`) that needs no codec —
-    what the synthetic dataset driver test and offline-decoded datasets use.  A real `.mp4` without torchvision
+    what the synthetic dataset driver test and offline-decoded datasets use; and the Motion-JPEG `.avi` files of
+    `video_io.write_mjpeg_avi` (what the generation drivers write without torchvision), decoded by PIL or, under
+    `video_io.set_jpeg_decoder("device")`, on the device.  A real `.mp4` without torchvision
     raises a RuntimeError naming the missing backend (no silent fallback).
 The crop / resize arithmetic (centre crop to the target aspect ratio with the reference's integer rounding, antialiased
 bilinear resize of the shorter side, centre crop) follows :118-196.
@@ -187,6 +189,27 @@ def load_audio_clips_uniformly(audio_path: str, clip_duration: float = 2.0, num_
 
 
 # ---- video ------------------------------------------------------------------------------------------------------------
+def _pick_frames(n_total: int, fps: float, t0: float, clip_duration: float, video_fps: int, n_frame: int) -> List[int]:
+    """The frame-picking rule of load_video_clip_from_videoreader (:199-231) over frame indices: walk the frames with pts in
+    [t0, t0 + duration + half a key-frame period], keep the first frame at or after each multiple of 1/video_fps,
+    repeat the last kept frame when the stream ends early."""
+    period = 1.0 / video_fps
+    picked, want = [], t0
+    first = max(int(np.floor(max(t0, 0.0) * fps)), 0)
+    for i in range(first, n_total):
+        pts = i / fps
+        if pts > t0 + clip_duration + period / 2.0:
+            break
+        if pts >= want:
+            picked.append(i)
+            want += period
+        if len(picked) == n_frame:
+            break
+    if not picked:
+        raise ValueError("no frame inside the requested clip window")
+    return picked + [picked[-1]] * (n_frame - len(picked))
+
+
 class _DecodedClip:
     """Pre-decoded container: frames uint8 (T, H, W, 3) at `fps`, optional audio f32 (C, Ta) at `audio_sr`."""
 
@@ -200,34 +223,58 @@ class _DecodedClip:
         self.audio_duration = self.audio.shape[1] / float(self.audio_sr) if self.audio is not None else self.video_duration
 
     def video_clip(self, t0: float, clip_duration: float, video_fps: int, n_frame: int) -> torch.Tensor:
-        """The frame-picking rule of load_video_clip_from_videoreader (:199-231): walk the frames with pts in
-        [t0, t0 + duration + half a key-frame period], keep the first frame at or after each multiple of 1/video_fps,
-        repeat the last kept frame when the stream ends early."""
-        period = 1.0 / video_fps
-        picked, want = [], t0
-        first = max(int(np.floor(max(t0, 0.0) * self.fps)), 0)
-        for i in range(first, self.frames.shape[0]):
-            pts = i / self.fps
-            if pts > t0 + clip_duration + period / 2.0:
-                break
-            if pts >= want:
-                picked.append(self.frames[i])
-                want += period
-            if len(picked) == n_frame:
-                break
-        if not picked:
-            raise ValueError("no frame inside the requested clip window")
-        picked += [picked[-1]] * (n_frame - len(picked))
-        return torch.from_numpy(np.stack(picked)).permute(0, 3, 1, 2).float() / 255.0
+        picked = _pick_frames(self.frames.shape[0], self.fps, t0, clip_duration, video_fps, n_frame)
+        return torch.from_numpy(np.stack([self.frames[i] for i in picked])).permute(0, 3, 1, 2).float() / 255.0
 
     def audio_clip(self, t0: float, clip_duration: float) -> torch.Tensor:
         a = self.audio[:, max(int(round(t0 * self.audio_sr)), 0):int(round((t0 + clip_duration) * self.audio_sr))]
         return _resample(a.contiguous(), self.audio_sr, 16000)
 
 
+class _MjpegClip(_DecodedClip):
+    """Motion-JPEG .avi as `video_io.write_mjpeg_avi` writes it: the container is walked once and the compressed frames kept; a clip
+    decodes only the frames it picks, with the decoder `video_io.set_jpeg_decoder` selects ("device": the clip is a device tensor)."""
+
+    def __init__(self, path: str):
+        from .video_io import walk_mjpeg_avi
+
+        self.jpegs, self.fps, pcm, nch, self.audio_sr = walk_mjpeg_avi(path)
+        if not self.jpegs or self.fps <= 0.0:
+            raise ValueError(f"{path}: no MJPG video stream")
+        self.audio = torch.from_numpy(np.frombuffer(pcm, dtype="<i2").reshape(-1, nch).T.astype(np.float32) / 32767.0) if nch else None
+        self.video_duration = len(self.jpegs) / self.fps
+        self.audio_duration = self.audio.shape[1] / float(self.audio_sr) if self.audio is not None else self.video_duration
+
+    def video_clip(self, t0: float, clip_duration: float, video_fps: int, n_frame: int) -> torch.Tensor:
+        from .video_io import decode_mjpeg_frames
+
+        picked = _pick_frames(len(self.jpegs), self.fps, t0, clip_duration, video_fps, n_frame)
+        distinct = sorted(set(picked))
+        frames = decode_mjpeg_frames([self.jpegs[i] for i in distinct])
+        if len(distinct) != len(picked):
+            frames = frames[torch.as_tensor([distinct.index(i) for i in picked], device=frames.device)]
+        frames = frames.permute(0, 3, 1, 2).float()
+        if frames.is_cuda:
+            # by a tensor: torch divides a device tensor by a Python scalar as a product with 1 / 255, which is not the host's
+            # quotient in the last bit; this is the IEEE division, so both decoders give the same clip
+            return frames / torch.full((), 255.0, device=frames.device)
+        return frames / 255.0
+
+
+def _is_mjpeg_avi(path: str) -> bool:
+    try:
+        with open(path, "rb") as f:
+            head = f.read(4096)                                   # the stream headers come first
+    except OSError:
+        return False
+    return head[:4] == b"RIFF" and head[8:12] == b"AVI " and b"vidsMJPG" in head.replace(b"vidsmjpg", b"vidsMJPG")
+
+
 def _open_video(video_path: str):
     if video_path.lower().endswith(".npz"):
         return _DecodedClip(video_path)
+    if video_path.lower().endswith(".avi") and _is_mjpeg_avi(video_path):
+        return _MjpegClip(video_path)
     try:
         import torchvision  # type: ignore  # noqa: F401
         from torchvision.io import VideoReader  # type: ignore  # noqa: F401

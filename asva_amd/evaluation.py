@@ -7,7 +7,8 @@ generated clips of each in sorted order, the first frame excluded from FID, the 
 
 Two deviations, both noted in INTEGRATION.md: the per-instance "IT" holds the IT value (the reference writes the IA value there,
 eval.py:269), and generated files are looked up with the groundtruth file's own extension (for `.mp4` names that is the reference's
-pattern), so that pre-decoded `.npz` clip containers work too.
+pattern), so that pre-decoded `.npz` clip containers work too; when no such file exists, the `.avi` files the generation drivers
+write without torchvision are taken.
 """
 from __future__ import annotations
 
@@ -25,7 +26,9 @@ FVD_MESSAGE = ("FVD needs the I3D detector, which is never downloaded: pass mode
 
 def _generated_paths(generated_video_root: str, groundtruth_video_name: str) -> List[str]:
     stem, ext = os.path.splitext(groundtruth_video_name)
-    return sorted(glob(f"{generated_video_root}/{stem}*{ext}"))
+    found = sorted(glob(f"{generated_video_root}/{stem}*{ext}"))
+    # without torchvision the generation drivers write Motion-JPEG .avi files (asva_amd.video_io), whatever the groundtruth is
+    return found or sorted(glob(f"{generated_video_root}/{stem}*.avi"))
 
 
 def reduce_metrics(groundtruth_fid_features: Optional[Sequence[torch.Tensor]] = None,

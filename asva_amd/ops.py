@@ -1550,6 +1550,66 @@ def jpeg_pack(coef: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     return stream, nbytes
 
 
+# ---- baseline JPEG decoder (csrc/jpeg.hip; host side in asva_amd/video_io.py) ------------------------------------------------
+JPEG_HUFF_SET_WORDS = 6 * 352      # AVSD_JPEG_HUFF_SET_WORDS: [component][DC, AC] tables of 352 words
+JPEG_SUBSEQ_BITS = 1024            # default length of a subsequence; any power of two in 128..4096 gives the same result
+JPEG_SAMPLINGS = {"444": (0, 3, 8), "420": (1, 6, 16)}     # name -> (AVSD_JPEG_4xx, blocks per MCU, MCU edge in pixels)
+
+
+def _jpeg_dev(name, t, dtypes, what):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{what}: {name} must be a device tensor (libavsd_hip.so has no host path)")
+    if t.dtype not in dtypes or not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be contiguous {dtypes[0]}, got {t.dtype}")
+
+
+def jpeg_decode_scan(scan: torch.Tensor, offsets: torch.Tensor, nbits: torch.Tensor, table_index: torch.Tensor, tables: torch.Tensor,
+                     blocks_per_frame: int, sampling: str, subseq_bits: int = JPEG_SUBSEQ_BITS, return_rounds: bool = False):
+    """scan uint8 (bytes,): the frames' entropy-coded segments without stuffing, frame f at offsets[f] (int64, multiples of 4) with
+    nbits[f] bits (int32) and at least 8 bytes of padding behind each; tables int32 (n_sets, 2112) as avsd.h describes them,
+    table_index int32 (n,) -> (coef int16 (n, blocks_per_frame, 64) zigzag, DC absolute; status int32 (n,), 0 = decoded[; rounds
+    int32 (n,)]).  See avsd_jpeg_decode_scan."""
+    what = "jpeg_decode_scan"
+    for name, t, dt in (("scan", scan, (torch.uint8,)), ("offsets", offsets, (torch.int64,)), ("nbits", nbits, (torch.int32,)),
+                        ("table_index", table_index, (torch.int32,)), ("tables", tables, (torch.int32, torch.uint32))):
+        _jpeg_dev(name, t, dt, what)
+    if sampling not in JPEG_SAMPLINGS:
+        raise ValueError(f"{what}: sampling must be one of {tuple(JPEG_SAMPLINGS)}, got {sampling!r}")
+    n = offsets.numel()
+    if n == 0 or nbits.numel() != n or table_index.numel() != n or tables.dim() != 2 or tables.shape[1] != JPEG_HUFF_SET_WORDS or scan.dim() != 1:
+        raise ValueError(f"{what}: offsets, nbits and table_index need one entry per frame and tables {JPEG_HUFF_SET_WORDS} words per set, got "
+                         f"{offsets.numel()}, {nbits.numel()}, {table_index.numel()}, {tuple(tables.shape)}")
+    coef = torch.empty((n, blocks_per_frame, 64), dtype=torch.int16, device=scan.device)
+    status = torch.empty((n,), dtype=torch.int32, device=scan.device)
+    rounds = torch.empty((n,), dtype=torch.int32, device=scan.device) if return_rounds else None
+    check(_lib.lib().avsd_jpeg_decode_scan(_p(scan), scan.numel(), _p(offsets), _p(nbits), _p(table_index), _p(tables), tables.shape[0], n,
+                                           blocks_per_frame, JPEG_SAMPLINGS[sampling][0], subseq_bits, _p(coef), _p(status),
+                                           _p(rounds) if return_rounds else None, _stream()), "avsd_jpeg_decode_scan")
+    return (coef, status, rounds) if return_rounds else (coef, status)
+
+
+def jpeg_idct_rgb(coef: torch.Tensor, H: int, W: int, sampling: str, qtabs: torch.Tensor, q_index: torch.Tensor) -> torch.Tensor:
+    """coef int16 (n, blocks, 64) of n frames of H x W -> uint8 (n, H, W, 3); qtabs int16 (n_sets, 3, 64): each component's
+    quantisation table in zigzag order, q_index int32 (n,).  See avsd_jpeg_idct_rgb_u8."""
+    what = "jpeg_idct_rgb"
+    for name, t, dt in (("coef", coef, (torch.int16,)), ("qtabs", qtabs, (torch.int16, torch.uint16)), ("q_index", q_index, (torch.int32,))):
+        _jpeg_dev(name, t, dt, what)
+    if sampling not in JPEG_SAMPLINGS:
+        raise ValueError(f"{what}: sampling must be one of {tuple(JPEG_SAMPLINGS)}, got {sampling!r}")
+    _, bpm, edge = JPEG_SAMPLINGS[sampling]
+    mcus = -(-H // edge) * -(-W // edge)
+    n = coef.shape[0]
+    if coef.dim() != 3 or n == 0 or tuple(coef.shape[1:]) != (mcus * bpm, 64) or qtabs.dim() != 3 or tuple(qtabs.shape[1:]) != (3, 64) \
+            or q_index.numel() != n:
+        raise ValueError(f"{what}: {H} x {W} {sampling} needs coef (n, {mcus * bpm}, 64), qtabs (sets, 3, 64) and n table indices, got "
+                         f"{tuple(coef.shape)}, {tuple(qtabs.shape)}, {q_index.numel()}")
+    planes = torch.empty((n * mcus * 64 * (edge * edge // 64 + 2),), dtype=torch.uint8, device=coef.device)
+    frames = torch.empty((n, H, W, 3), dtype=torch.uint8, device=coef.device)
+    check(_lib.lib().avsd_jpeg_idct_rgb_u8(_p(coef), n, H, W, JPEG_SAMPLINGS[sampling][0], _p(qtabs), qtabs.shape[0], _p(q_index), _p(planes),
+                                           planes.numel(), _p(frames), _stream()), "avsd_jpeg_idct_rgb_u8")
+    return frames
+
+
 def patchify(x: torch.Tensor, kh: int, kw: int, stride: int) -> torch.Tensor:
     """(B, C, H, W) f32 -> bf16 rows [B*ph*pw, C*kh*kw]."""
     _req(x, F32, "x")

@@ -17,9 +17,10 @@ from __future__ import annotations
 
 import io
 import os
+import re
 import struct
 import warnings
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -227,18 +228,270 @@ def write_mjpeg_avi(filename: str, video_array, fps: float, audio_array=None, au
     return filename
 
 
-def read_mjpeg_avi(filename: str) -> Tuple[torch.Tensor, float, Optional[torch.Tensor], int]:
-    """-> (video (T, H, W, 3) uint8, fps, audio (C, Ta) float or None, audio_fps) of a file written above."""
-    from PIL import Image
+# ---- where the frames are decoded ----------------------------------------------------------------------------------------
+_JPEG_DECODERS = ("host", "device")
+_jpeg_decoder = "host"
+_DEC_NEEDS_GPU = ('the "device" JPEG decoder needs the GPU (torch.cuda.is_available() is False) and has no host path; '
+                  'use "host"')
 
+
+def set_jpeg_decoder(mode: str) -> None:
+    """Who decodes the frames `read_mjpeg_avi` and the clip loaders (data_utils._MjpegClip) return.  "host": PIL, host tensors,
+    the default.  "device": `decode_jpeg_frames` (avsd_jpeg_decode_scan + avsd_jpeg_idct_rgb_u8), device tensors; needs a GPU.
+    Read once from $AVSD_JPEG_DECODER at import."""
+    global _jpeg_decoder
+    if mode not in _JPEG_DECODERS:
+        raise ValueError(f"set_jpeg_decoder: unknown mode {mode!r}; one of {_JPEG_DECODERS}")
+    if mode == "device" and not torch.cuda.is_available():
+        raise RuntimeError(f'set_jpeg_decoder("device"): {_DEC_NEEDS_GPU}')
+    _jpeg_decoder = mode
+
+
+def get_jpeg_decoder() -> str:
+    return _jpeg_decoder
+
+
+def _decoder_from_env(environ=os.environ) -> None:
+    if environ.get("AVSD_JPEG_DECODER"):
+        set_jpeg_decoder(environ["AVSD_JPEG_DECODER"])
+
+
+_decoder_from_env()
+
+_NEXT_MARKER = re.compile(rb"\xff[^\x00\xff]")
+
+
+def parse_jpeg(data: bytes) -> dict:
+    """The markers of one JPEG file, for the device decoder -> {"H", "W", "sampling": "444" | "420", "qtabs": the three components'
+    quantisation tables (64 entries each, zigzag order, as bytes), "huff": the three components' ((DC BITS, HUFFVAL), (AC BITS,
+    HUFFVAL)) as bytes, "scan": the entropy-coded segment with its FF 00 stuffing}.  Accepts SOI, APPn / COM, DQT with 8-bit
+    entries, SOF0 with 8-bit samples and three components sampled (1x1, 1x1, 1x1) or (2x2, 1x1, 1x1), DHT, DRI of 0, one
+    interleaved SOS with Ss = 0, Se = 63, Ah = Al = 0, EOI.  Anything else raises ValueError naming what was found."""
+    def bad(what):
+        return ValueError(f"parse_jpeg: {what}; the device decoder takes baseline JPEG with three components, 4:4:4 or 4:2:0, one scan, "
+                          "no restart interval")
+
+    if data[:2] != b"\xff\xd8":
+        raise bad(f"the file starts with {bytes(data[:2]).hex()}, not with SOI")
+    p, dqt, dht, sof, sos = 2, {}, {}, None, None
+    while sos is None:
+        if p + 4 > len(data):
+            raise bad("the file ends before SOS")
+        if data[p] != 0xFF:
+            raise bad(f"byte {data[p]:#04x} at {p} where a marker was expected")
+        m = data[p + 1]
+        if m == 0xFF:                                             # fill byte
+            p += 1
+            continue
+        n = struct.unpack(">H", data[p + 2:p + 4])[0]
+        seg = data[p + 4:p + 2 + n]
+        if n < 2 or len(seg) != n - 2:
+            raise bad(f"segment {m:#04x} at {p} is cut short")
+        if 0xE0 <= m <= 0xEF or m == 0xFE:
+            pass
+        elif m == 0xDB:
+            q = 0
+            while q < len(seg):
+                if seg[q] >> 4 or len(seg) < q + 65:
+                    raise bad("a quantisation table with 16-bit entries" if seg[q] >> 4 else "a DQT segment that is cut short")
+                dqt[seg[q] & 15] = bytes(seg[q + 1:q + 65])
+                q += 65
+        elif m == 0xC4:
+            q = 0
+            while q < len(seg):
+                bits = bytes(seg[q + 1:q + 17])
+                cnt = sum(bits)
+                if len(bits) != 16 or cnt > 256 or len(seg) < q + 17 + cnt or seg[q] & 0xEE:
+                    raise bad(f"a DHT segment that is cut short or names table {seg[q]:#04x}")
+                dht[seg[q]] = (bits, bytes(seg[q + 17:q + 17 + cnt]))
+                q += 17 + cnt
+        elif m == 0xC0:
+            if len(seg) < 6 or seg[0] != 8 or seg[5] != 3 or len(seg) != 15:
+                raise bad(f"SOF0 with {seg[0] if seg else '?'}-bit samples and {seg[5] if len(seg) > 5 else '?'} component(s)")
+            sof = seg
+        elif m == 0xDD:
+            if len(seg) != 2 or seg[0] or seg[1]:
+                raise bad(f"a restart interval (DRI {struct.unpack('>H', seg[:2])[0] if len(seg) >= 2 else '?'})")
+        elif m == 0xDA:
+            if sof is None:
+                raise bad("SOS before SOF0")
+            if len(seg) != 10 or seg[0] != 3 or bytes(seg[7:10]) != b"\x00\x3f\x00":
+                raise bad(f"a scan of {seg[0] if seg else '?'} component(s) with Ss, Se, AhAl = {bytes(seg[-3:]).hex()} (not one interleaved "
+                          "sequential scan)")
+            sos = seg
+        elif 0xC1 <= m <= 0xCF:
+            name = {0xC1: "extended sequential", 0xC2: "progressive", 0xC3: "lossless", 0xC9: "arithmetic coding", 0xCA: "arithmetic coding",
+                    0xCB: "arithmetic coding", 0xCC: "arithmetic coding (DAC)"}.get(m, "differential / arithmetic")
+            raise bad(f"marker {m:#04x}: {name}")
+        else:
+            raise bad(f"marker {m:#04x} at {p}")
+        p += 2 + n
+    H, W = struct.unpack(">HH", sof[1:5])
+    comps = [(sof[6 + 3 * i], sof[7 + 3 * i], sof[8 + 3 * i]) for i in range(3)]
+    samp = tuple(c[1] for c in comps)
+    if samp not in ((0x11, 0x11, 0x11), (0x22, 0x11, 0x11)):
+        raise bad("sampling factors " + ", ".join(f"{s >> 4}x{s & 15}" for s in samp))
+    if H < 1 or W < 1:
+        raise bad(f"a frame of {H} x {W}")
+    qtabs, huff = [], []
+    for i, (cid, _s, tq) in enumerate(comps):
+        if sos[1 + 2 * i] != cid:
+            raise bad("a scan whose components are not in the frame's order")
+        td, ta = sos[2 + 2 * i] >> 4, sos[2 + 2 * i] & 15
+        if tq not in dqt or td not in dht or (0x10 | ta) not in dht:
+            raise bad(f"component {i} refers to a table that is missing (quantisation {tq}, DC {td}, AC {ta})")
+        qtabs.append(dqt[tq])
+        huff.append((dht[td], dht[0x10 | ta]))
+    m = _NEXT_MARKER.search(data, p)
+    if m is None:
+        raise bad("no EOI behind the scan")
+    if data[m.start() + 1] != 0xD9:
+        raise bad(f"marker {data[m.start() + 1]:#04x} inside or behind the scan (restart markers or a further scan)")
+    return {"H": H, "W": W, "sampling": "444" if samp[0] == 0x11 else "420", "qtabs": tuple(qtabs), "huff": tuple(huff),
+            "scan": bytes(data[p:m.start()])}
+
+
+def huffman_decode_table(bits: bytes, vals: bytes, dc: bool) -> np.ndarray:
+    """(BITS, HUFFVAL) -> the 352 words of avsd.h: lut[256], limit[16], offset[16], vals[64]; codes by the procedure of Annex C"""
+    out = np.zeros(352, dtype=np.uint32)
+    code, k = 0, 0
+    for length in range(1, 17):
+        cnt = bits[length - 1]
+        out[272 + length - 1] = (k - code) & 0xFFFFFFFF
+        if length <= 8:
+            for _ in range(cnt):
+                lo = code << (8 - length)
+                out[lo:lo + (1 << (8 - length))] = (length << 8) | vals[k]
+                code += 1
+                k += 1
+        else:
+            code += cnt
+            k += cnt
+        if code > 1 << length:
+            raise ValueError("parse_jpeg: a Huffman table with more codes than its lengths allow")
+        out[256 + length - 1] = code << (16 - length)
+        code <<= 1
+    if dc and any(v > 11 for v in vals):
+        raise ValueError(f"parse_jpeg: a DC Huffman table with category {max(vals)} (baseline has 0..11)")
+    out[288:] = np.frombuffer(bytes(vals).ljust(256, b"\0"), dtype="<u4")
+    return out
+
+
+_dec_cache = {}
+
+
+def _decode_tables(key, build, device):
+    """one upload per distinct table set and device"""
+    k = (key, str(device))
+    if k not in _dec_cache:
+        if len(_dec_cache) > 256:
+            _dec_cache.clear()
+        _dec_cache[k] = build()
+    return _dec_cache[k]
+
+
+def _stack(ts):
+    return ts[0][None] if len(ts) == 1 else torch.stack(ts)
+
+
+JPEG_STATUS = {1: "a code no table assigns", 2: "more blocks than the frame has", 4: "a run behind coefficient 63",
+               8: "the scan ends before the last block", 16: "bits left over behind the last block", 32: "arguments out of range"}
+
+
+def _entropy_decode(jpegs, device, subseq_bits, counters, infos):
+    """parse, unstuff, upload, avsd_jpeg_decode_scan -> (H, W, sampling, coef, status, qtabs, q_index), all tensors on the device"""
+    from . import ops
+
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"decode_jpeg_frames: {_DEC_NEEDS_GPU}")
+    if len(jpegs) == 0:
+        raise ValueError("decode_jpeg_frames: no frames")
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise ValueError(f"decode_jpeg_frames: device must be a GPU, got {device}")
+    infos = infos or [parse_jpeg(j) for j in jpegs]
+    H, W, sampling = infos[0]["H"], infos[0]["W"], infos[0]["sampling"]
+    for t, i in enumerate(infos):
+        if (i["H"], i["W"], i["sampling"]) != (H, W, sampling):
+            raise ValueError(f"decode_jpeg_frames: frame {t} is {i['H']} x {i['W']} {i['sampling']}, frame 0 is {H} x {W} {sampling}; all "
+                             "frames of a call have one size and one sampling")
+    _, bpm, edge = ops.JPEG_SAMPLINGS[sampling]
+    blocks = -(-H // edge) * -(-W // edge) * bpm
+    scans = [i["scan"].replace(b"\xff\x00", b"\xff") for i in infos]
+    if max(len(sc) for sc in scans) * 8 > 1 << 30:
+        raise ValueError("decode_jpeg_frames: a scan longer than 2^30 bits")
+    offsets, buf = [], bytearray()
+    for sc in scans:
+        offsets.append(len(buf))
+        buf += sc + b"\xff" * ((-len(sc)) % 8 + 8)                 # 8 bytes the bit reader may touch; 8-byte alignment for what follows
+    hkeys, qkeys, hidx, qidx = {}, {}, [], []
+    for i in infos:
+        hidx.append(hkeys.setdefault(i["huff"], len(hkeys)))
+        qidx.append(qkeys.setdefault(i["qtabs"], len(qkeys)))
+    htabs = _stack([_decode_tables(("h", k), lambda k=k: torch.from_numpy(np.concatenate(
+        [huffman_decode_table(*spec, dc=(j == 0)) for comp in k for j, spec in enumerate(comp)]).view(np.int32)).to(device), device) for k in hkeys])
+    qtabs = _stack([_decode_tables(("q", k), lambda k=k: torch.tensor([list(q) for q in k], dtype=torch.int16, device=device), device)
+                    for k in qkeys])
+    T, n_scan = len(jpegs), len(buf)
+    buf += np.asarray(offsets, dtype="<i8").tobytes()              # the scans and the per-frame words: one upload
+    buf += np.asarray([8 * len(sc) for sc in scans] + hidx + qidx, dtype="<i4").tobytes()
+    up = torch.frombuffer(buf, dtype=torch.uint8).to(device)
+    words = up[n_scan + 8 * T:].view(torch.int32)
+    coef, status, *rounds = ops.jpeg_decode_scan(up[:n_scan], up[n_scan:n_scan + 8 * T].view(torch.int64), words[:T], words[T:2 * T], htabs, blocks,
+                                                 sampling, subseq_bits or ops.JPEG_SUBSEQ_BITS, return_rounds=counters is not None)
+    if counters is not None:
+        counters["upload_bytes"] = len(buf)
+        counters["rounds"] = rounds[0]
+    return H, W, sampling, coef, status, qtabs, words[2 * T:3 * T]
+
+
+def _check_status(status, counters) -> None:
+    """the one copy back: the status words (and the round counters, when asked for)"""
+    if counters is not None:
+        counters["rounds"] = counters["rounds"].cpu().tolist()
+    for t, s in enumerate(status.cpu().tolist()):
+        if s:
+            why = ", ".join(v for b, v in JPEG_STATUS.items() if s & b)
+            raise ValueError(f"decode_jpeg_frames: frame {t} did not decode (status {s}: {why})")
+
+
+def decode_jpeg_coefficients(jpegs: Sequence[bytes], device=None, subseq_bits: Optional[int] = None, counters: Optional[dict] = None) -> torch.Tensor:
+    """The first half of `decode_jpeg_frames`: T complete JPEG files -> int16 (T, blocks, 64) on the device, the quantised
+    coefficients in zigzag order, blocks in scan order, DC values absolute."""
+    _H, _W, _sampling, coef, status, _q, _qi = _entropy_decode(jpegs, device, subseq_bits, counters, None)
+    _check_status(status, counters)
+    return coef
+
+
+def decode_jpeg_frames(jpegs: Sequence[bytes], device=None, subseq_bits: Optional[int] = None, counters: Optional[dict] = None,
+                       _infos=None) -> torch.Tensor:
+    """T complete JPEG files of one size and one sampling -> uint8 (T, H, W, 3) on the device, decoded there.
+
+    The host parses the markers (`parse_jpeg`: baseline, three components, 4:4:4 or 4:2:0; anything else raises ValueError), removes
+    the FF 00 stuffing, concatenates the scans into one padded buffer (one upload, with the per-frame offsets, bit lengths and table
+    indices), and builds the Huffman decode tables; quantisation and Huffman tables may differ from frame to frame, each distinct
+    set is uploaded once per process.  Two entry points (ops.jpeg_decode_scan, ops.jpeg_idct_rgb: three launches), then one copy to
+    the host: the T status words.  A stream that does not decode raises ValueError naming the first such frame.  The pixels are
+    the ones PIL returns for the same files.  `subseq_bits`: see ops.jpeg_decode_scan; the result does not depend on it.
+    `counters`, if given, receives "upload_bytes" and "rounds" (the re-decoding rounds of each frame, copied back with the status)."""
+    from . import ops
+
+    H, W, sampling, coef, status, qtabs, q_index = _entropy_decode(jpegs, device, subseq_bits, counters, _infos)
+    frames = ops.jpeg_idct_rgb(coef, H, W, sampling, qtabs, q_index)
+    _check_status(status, counters)
+    return frames
+
+
+def walk_mjpeg_avi(filename: str) -> Tuple[List[bytes], float, bytes, int, int]:
+    """The container walk of a file written above -> (compressed frames, fps, interleaved 16-bit PCM, channels, audio rate)."""
     with open(filename, "rb") as f:
         data = f.read()
     if data[:4] != b"RIFF" or data[8:12] != b"AVI ":
         raise ValueError(f"{filename}: not a RIFF/AVI file")
-    frames, pcm, fps, nch, afps = [], b"", 0.0, 0, 16000
+    frames, pcm, fps, nch, afps, codec = [], b"", 0.0, 0, 16000, None
 
     def walk(lo: int, hi: int):
-        nonlocal pcm, fps, nch, afps
+        nonlocal pcm, fps, nch, afps, codec
         p = lo
         while p + 8 <= hi:
             tag, n = data[p:p + 4], struct.unpack("<I", data[p + 4:p + 8])[0]
@@ -246,18 +499,59 @@ def read_mjpeg_avi(filename: str) -> Tuple[torch.Tensor, float, Optional[torch.T
             if tag == b"LIST":
                 walk(body + 4, body + n)
             elif tag == b"strh" and data[body:body + 4] == b"vids":
+                codec = data[body + 4:body + 8]
                 scale, rate = struct.unpack("<II", data[body + 20:body + 28])
                 fps = rate / scale
             elif tag == b"strf" and n == 18:
                 _, nch, afps = struct.unpack("<HHI", data[body:body + 8])
             elif tag == b"00dc":
-                frames.append(np.array(Image.open(io.BytesIO(data[body:body + n])).convert("RGB")))
+                frames.append(data[body:body + n])
             elif tag == b"01wb":
                 pcm += data[body:body + n]
             p = body + n + (n & 1)
 
     walk(12, len(data))
-    video = torch.from_numpy(np.stack(frames))
+    if codec is not None and codec.upper() != b"MJPG":
+        raise ValueError(f"{filename}: the video stream is {codec!r}, not MJPG")
+    return frames, fps, pcm, nch, afps
+
+
+_warned_format = False
+
+
+def decode_mjpeg_frames(frames: Sequence[bytes], decoder: Optional[str] = None, device=None) -> torch.Tensor:
+    """The decode step: compressed frames -> uint8 (T, H, W, 3).  `decoder`: "host" (PIL, a host tensor) or "device"
+    (`decode_jpeg_frames`, a device tensor); None = the `set_jpeg_decoder` setting.  "device" leaves files the device decoder
+    refuses (progressive, greyscale, 4:2:2, restart markers, ...) to PIL and uploads the result, with one warning per process."""
+    global _warned_format
+    mode = _jpeg_decoder if decoder is None else decoder
+    if mode not in _JPEG_DECODERS:
+        raise ValueError(f"decode_mjpeg_frames: unknown decoder {mode!r}; one of {_JPEG_DECODERS}")
+    if mode == "device":
+        if not torch.cuda.is_available():
+            raise RuntimeError(f'decode_mjpeg_frames(decoder="device"): {_DEC_NEEDS_GPU}')
+        try:
+            infos = [parse_jpeg(f) for f in frames]
+            if len({(i["H"], i["W"], i["sampling"]) for i in infos}) > 1:
+                raise ValueError("parse_jpeg: frames of different sizes or samplings in one file")
+        except ValueError as e:
+            if not _warned_format:
+                warnings.warn(f"the device JPEG decoder does not take this file ({e}): PIL decodes it and the frames are uploaded",
+                              RuntimeWarning, stacklevel=3)
+                _warned_format = True
+        else:
+            return decode_jpeg_frames(frames, device, _infos=infos)
+    from PIL import Image
+
+    video = torch.from_numpy(np.stack([np.array(Image.open(io.BytesIO(f)).convert("RGB")) for f in frames]))
+    return video.to(torch.device("cuda" if device is None else device)) if mode == "device" else video
+
+
+def read_mjpeg_avi(filename: str, decoder: Optional[str] = None, device=None) -> Tuple[torch.Tensor, float, Optional[torch.Tensor], int]:
+    """-> (video (T, H, W, 3) uint8, fps, audio (C, Ta) float or None, audio_fps) of a file written above.  `decoder`, `device`: see
+    `decode_mjpeg_frames`; with the "host" decoder (the default setting) the video is a host tensor decoded by PIL."""
+    frames, fps, pcm, nch, afps = walk_mjpeg_avi(filename)
+    video = decode_mjpeg_frames(frames, decoder, device)
     audio = None
     if nch:
         audio = torch.from_numpy(np.frombuffer(pcm, dtype="<i2").reshape(-1, nch).T.astype(np.float32) / 32767.0)

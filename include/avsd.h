@@ -668,6 +668,56 @@ int avsd_jpeg_quantize_u8(const void* frames_u8, int n, int H, int W, const uint
 int avsd_jpeg_pack_i16(const int16_t* coef, int n, int blocks_per_frame, void* scratch, int64_t scratch_bytes, void* out_u8,
                        int64_t out_stride, int32_t* nbytes, void* stream);
 
+/* ---- baseline JPEG decoder for the clip readers (csrc/jpeg.hip; asva_amd/video_io.py:decode_jpeg_frames) --------------------
+ * Baseline sequential DCT, 8-bit, three components, one interleaved scan, no restart markers; 4:4:4 (an MCU is Y, Cb, Cr) or
+ * 4:2:0 (an MCU is four Y blocks in raster order, Cb, Cr).  Integer arithmetic only: both builds give the same bytes, and for a
+ * stream an encoder made from pixels they are the bytes libjpeg-turbo returns.  Markers, the removal of FF 00 stuffing and the
+ * construction of the Huffman decode tables are the caller's. */
+#define AVSD_JPEG_444 0
+#define AVSD_JPEG_420 1
+#define AVSD_JPEG_MAX_SCAN_BITS (1 << 30)
+/* One Huffman table as 32-bit words: lut[256] indexed by the next 8 bits, (length << 8) | symbol for codes of up to 8 bits, else
+ * 0; limit[16], limit[l - 1] = the first 16-bit left-aligned value that no code of length <= l starts; offset[16],
+ * offset[l - 1] = (index in HUFFVAL of the first code of length l) - (that code), so that code + offset indexes HUFFVAL;
+ * vals[64]: HUFFVAL as 256 bytes, little-endian in the words.  A set is [component 0..2][DC, AC]. */
+#define AVSD_JPEG_HUFF_WORDS 352
+#define AVSD_JPEG_HUFF_SET_WORDS (6 * AVSD_JPEG_HUFF_WORDS)
+/* bits of status[f]; 0 = the frame decoded */
+#define AVSD_JPEG_BAD_CODE 1    /* a prefix no code of the table has (the decoder moved on by one bit)                     */
+#define AVSD_JPEG_TOO_MANY 2    /* more than blocks_per_frame blocks (nothing was written for them)                        */
+#define AVSD_JPEG_BAD_INDEX 4   /* a run that leads behind coefficient 63                                                  */
+#define AVSD_JPEG_INCOMPLETE 8  /* not exactly blocks_per_frame whole blocks                                               */
+#define AVSD_JPEG_BAD_TAIL 16   /* eight or more bits, or a zero bit, behind the last block                                */
+#define AVSD_JPEG_BAD_ARGS 32   /* offset, bit length or table index of the frame out of range: nothing was read           */
+/* scan: the n entropy-coded segments, stuffing removed, frame f at byte offsets[f] (a multiple of 4) with nbits[f] bits (8 x its
+ * bytes, at most AVSD_JPEG_MAX_SCAN_BITS); behind every segment at least 8 bytes of padding inside scan_bytes (any value: bits
+ * behind the end read as ones).  table_index[f] < n_tables selects the frame's set in tables u32 [n_tables][SET_WORDS].
+ * offsets i64, nbits / table_index i32, all on the device.  -> coef i16 [n][blocks_per_frame][64] in zigzag order, blocks in
+ * scan order, DC values absolute (the predictor is per component and starts at 0 in every frame); status i32 [n]; rounds i32 [n]
+ * or NULL: the largest number of re-decoding rounds any chunk of the frame needed.  coef 16-byte aligned.
+ * One launch, one workgroup of 1024 lanes per frame: the scan is cut into subsequences of subseq_bits bits (a power of two in
+ * 128..4096), 1024 at a time; each lane decodes one from a guessed state, lanes whose predecessor ended elsewhere decode again
+ * until nothing changes (at most 1023 rounds), a prefix sum of the completed blocks places the stores of a last pass, and a
+ * per-component prefix sum undoes the DC prediction.  The result does not depend on subseq_bits.  Every loop is bounded by the
+ * bit length; a symbol that would end behind the last bit is not decoded; every store is index-checked, so a damaged stream
+ * sets status[f] and writes only inside frame f's coefficients.  The checks of this entry point cover the host arguments; the
+ * per-frame device arguments are checked by the kernel (AVSD_JPEG_BAD_ARGS). */
+int avsd_jpeg_decode_scan(const void* scan, int64_t scan_bytes, const int64_t* offsets, const int32_t* nbits, const int32_t* table_index,
+                          const uint32_t* tables, int n_tables, int n, int blocks_per_frame, int sampling, int subseq_bits, int16_t* coef,
+                          int32_t* status, int32_t* rounds, void* stream);
+/* coef as written above for n frames of H x W (blocks_per_frame = MCUs x 3 or 6, MCUs = ceil(H / 8v) x ceil(W / 8v), v = 1 for
+ * 4:4:4 and 2 for 4:2:0) -> frames u8 [n][H][W][3] (R, G, B).  qtabs u16 [n_qsets][3][64]: the quantisation table of each
+ * component in ZIGZAG order (as a DQT segment carries it); q_index i32 [n] on the device selects a frame's set (out of range:
+ * set 0).  planes: scratch of at least n x MCUs x 64 x (v * v + 2) bytes, 8-byte aligned.  Two launches.  The first dequantises
+ * and runs libjpeg's "islow" IDCT (13-bit constants, descaling by 11 bits down the columns and by 18 along the rows, + 128,
+ * clamped) into whole-MCU planes; products, i0 +- i4, z3, z4 wrap to 16 bits, pass results saturate to 16 bits and a block
+ * without AC in rows 1..7 is row 0 << 2, as in libjpeg-turbo's vector code (no-ops for streams made from pixels).  The second
+ * upsamples 4:2:0 chroma with libjpeg's triangle filter over the ceil(H/2) x ceil(W/2) real samples (edges repeated) and
+ * converts with R = Y + ((91881 Cr + 32768) >> 16), G = Y + ((-22554 Cb - 46802 Cr + 32768) >> 16),
+ * B = Y + ((116130 Cb + 32768) >> 16), Cb and Cr less 128, clamped. */
+int avsd_jpeg_idct_rgb_u8(const int16_t* coef, int n, int H, int W, int sampling, const uint16_t* qtabs, int n_qsets, const int32_t* q_index,
+                          void* planes, int64_t planes_bytes, void* frames_u8, void* stream);
+
 /* ---- launch plans (a host without Python runs the path) ----------------------------------------------------
  * A plan is the sequence of calls to the entry points above that one operation of the reference issues — the UNet forward
  * of a denoising step (audio_cond_unet_3d_condition.py:598-798), the per-clip conditioning projections, the VAE decode
