@@ -114,6 +114,7 @@ SIGNATURES = {
     "avsd_guided_unipc": (c_int, [c_void_p, c_int, c_float, c_float, c_void_p, c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float),
                                   C.POINTER(C.c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float,
                                   c_float, c_float, c_int, c_int, c_int, c_int, c_void_p]),
+    "avsd_window_turnover": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_int, c_void_p]),
     "avsd_vae_postprocess":(c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     "avsd_vae_postprocess_u8": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     "avsd_kaldi_fbank": (c_int, [c_void_p, c_int, c_int, C.c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int,

@@ -262,6 +262,45 @@ __global__ void copy_rep_kernel(const uint4* src, uint4* dst, int64_t nvec, int 
   }
 }
 
+// four f32 with the alignment of one: a frame row starts at a multiple of HW floats, which is 16-byte aligned only when HW % 4 == 0
+typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+
+// Turnover between two chained windows (include/avsd.h).  One work item = up to 4 consecutive floats of one (b, c, unit) row;
+// unit 0 moves frame F-1 of x_prev to frame 0 of x_next AND writes frame F-1 of x_next, in that order and in the same thread, so
+// that x_next == x_prev is safe: nobody else touches that piece of frame F-1.  Unit u >= 1 writes frame u (1 <= u <= F-2).
+// The last item of a row (v == nvec) is the scalar tail of HW % 4 floats.
+__global__ void window_turnover_kernel(const float* x_prev, const float* noise, float* x_next, float sigma, int F, int HW,
+                                       int units, int per_row, int64_t total) {
+  const int nvec = HW / 4;
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+    const int v = (int)(t % per_row);
+    const int u = (int)((t / per_row) % units);
+    const int64_t bc = t / ((int64_t)per_row * units);
+    const int64_t xrow = bc * F * HW;               // (b, c) slab of the latents: F rows of HW
+    const int64_t nrow = bc * (F - 1) * HW;         // ... of the noise: F - 1 rows
+    const int fn = (u == 0) ? F - 1 : u;            // the frame this item fills with noise (none when F == 1)
+    if (v < nvec) {
+      const int o = v * 4;
+      if (u == 0) {
+        const f32x4_a4 last = *reinterpret_cast<const f32x4_a4*>(x_prev + xrow + (int64_t)(F - 1) * HW + o);
+        *reinterpret_cast<f32x4_a4*>(x_next + xrow + o) = last;
+      }
+      if (fn >= 1) {
+        const f32x4_a4 n4 = *reinterpret_cast<const f32x4_a4*>(noise + nrow + (int64_t)(fn - 1) * HW + o);
+        *reinterpret_cast<f32x4_a4*>(x_next + xrow + (int64_t)fn * HW + o) = n4 * sigma;
+      }
+    } else {
+      for (int o = nvec * 4; o < HW; ++o) {
+        if (u == 0) {
+          const float last = x_prev[xrow + (int64_t)(F - 1) * HW + o];
+          x_next[xrow + o] = last;
+        }
+        if (fn >= 1) x_next[xrow + (int64_t)fn * HW + o] = noise[nrow + (int64_t)(fn - 1) * HW + o] * sigma;
+      }
+    }
+  }
+}
+
 // one thread per (block b, key slot j < lk_pad, 8-channel chunk): K rows copied as they are, V written transposed; the
 // padding slots j >= lk are written as zeros on every call (the fused kernel multiplies p = 0 by the V^T padding, so it
 // must be finite whatever the allocator handed out — a replaying host binds fresh memory)
@@ -455,6 +494,25 @@ extern "C" int avsd_copy(const void* src, void* dst, int64_t bytes, int rep, voi
   hipLaunchKernelGGL(copy_rep_kernel, dim3(grid_for(nvec, 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      (const uint4*)src, (uint4*)dst, nvec, rep);
   AVSD_CHECK_LAUNCH("copy launch");
+  return AVSD_OK;
+}
+
+extern "C" int avsd_window_turnover(const float* x_prev, const float* noise, float* x_next, float sigma, int B, int C, int F, int HW,
+                                    void* stream) {
+  AVSD_REQUIRE(x_prev && x_next, "window_turnover: null pointer");
+  AVSD_REQUIRE(B > 0 && C > 0 && F > 0 && HW > 0, "window_turnover: bad shape");
+  AVSD_REQUIRE(noise || F == 1, "window_turnover: frames 1.. need noise");
+  AVSD_REQUIRE(((uintptr_t)x_prev | (uintptr_t)x_next | (uintptr_t)noise) % 4 == 0, "window_turnover: pointers must be 4-byte aligned");
+  const int64_t xbytes = (int64_t)B * C * F * HW * 4, nbytes = (int64_t)B * C * (F - 1) * HW * 4;
+  const uintptr_t xp = (uintptr_t)x_prev, xn = (uintptr_t)x_next, nz = (uintptr_t)noise;
+  AVSD_REQUIRE(xp == xn || xp + xbytes <= xn || xn + xbytes <= xp, "window_turnover: x_next must equal x_prev or not overlap it");
+  AVSD_REQUIRE(nbytes == 0 || nz + nbytes <= xn || xn + xbytes <= nz, "window_turnover: noise must not overlap x_next");
+  const int units = F > 2 ? F - 1 : 1;
+  const int per_row = (HW + 3) / 4;
+  const int64_t total = (int64_t)B * C * units * per_row;
+  hipLaunchKernelGGL(window_turnover_kernel, dim3(grid_for(total, 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     x_prev, noise, x_next, sigma, F, HW, units, per_row, total);
+  AVSD_CHECK_LAUNCH("window_turnover launch");
   return AVSD_OK;
 }
 

@@ -73,6 +73,7 @@ const Entry kEntries[] = {
     AVSD_PLAN_ENTRY(avsd_vae_postprocess_u8_x2), AVSD_PLAN_ENTRY(avsd_softmax_rows_x2),
     AVSD_PLAN_ENTRY(avsd_groupnorm_fused),  AVSD_PLAN_ENTRY(avsd_groupnorm_fused_x2),
     AVSD_PLAN_ENTRY(avsd_ln_fold),          AVSD_PLAN_ENTRY(avsd_guided_multistep),      AVSD_PLAN_ENTRY(avsd_guided_unipc),
+    AVSD_PLAN_ENTRY(avsd_window_turnover),
     // AVSync scorer (csrc/avsync.hip)
     AVSD_PLAN_ENTRY(avsd_convnd_f32),       AVSD_PLAN_ENTRY(avsd_maxpool_hw_f32),        AVSD_PLAN_ENTRY(avsd_mean_rows_f32),
     AVSD_PLAN_ENTRY(avsd_resize_aa_normalize_f32),

@@ -175,6 +175,25 @@ def _clip_starts(duration: float, clip_duration: float, num_clips: int) -> np.nd
     return np.linspace(0.0, duration - clip_duration, endpoint=True, num=num_clips)
 
 
+def track_windows(n_samples: int, sample_rate: int = 16000, video_fps: int = 6, video_num_frame: int = 12):
+    """Chained windows that cover a whole audio track (AudioCondAnimationPipeline.animate_track), in integer arithmetic.
+
+    With F = video_num_frame, window k makes output frames [k (F-1), k (F-1) + F-1] from the audio samples [s_k, s_k + F sr // fps),
+    s_k = (k (F-1) sr) // fps: frame k (F-1) is the last frame of window k-1 and the first of window k, and the audio of window k
+    starts at that frame's own time.  The track is zero-padded at the tail to fill the last window; the frames of the padding are
+    trimmed from the output, but never below one window.
+    -> ([(s_k, first_frame_k)] * W, W, n_frames, padded length in samples)."""
+    n, sr, fps, F = int(n_samples), int(sample_rate), int(video_fps), int(video_num_frame)
+    if n < 0 or sr <= 0 or fps <= 0 or F < 2:
+        raise ValueError(f"track_windows: need n_samples >= 0, sample_rate > 0, video_fps > 0 and video_num_frame >= 2, got {(n, sr, fps, F)}")
+    win = F * sr // fps
+    hop_num = (F - 1) * sr                                  # the hop is hop_num / fps samples
+    W = 1 + (max(0, n - win) * fps + hop_num - 1) // hop_num
+    n_frames = min(1 + W * (F - 1), max(F, (n * fps + sr - 1) // sr))
+    windows = [((k * hop_num) // fps, k * (F - 1)) for k in range(W)]
+    return windows, W, n_frames, windows[-1][0] + win
+
+
 def load_audio_clips_uniformly(audio_path: str, clip_duration: float = 2.0, num_clips: int = 1,
                                load_audio_as_melspectrogram: bool = True):
     """-> (b, 1, n, t) mel-spectrograms, or a list of b waveforms (c, t) at 16 kHz (:389-424)."""

@@ -40,6 +40,7 @@ class DenoiseEngine:
         self.use_graph = use_graph and torch.cuda.is_available() and not getattr(ops, "EMULATED", False)
         self._graph = None
         self._graph_key = None
+        self.captures = 0      # hipGraphs built so far: stays 1 while clips (or the windows of a track) keep one geometry
 
     # -- once per clip ---------------------------------------------------------------------------------
     def set_conditioning(self, text: torch.Tensor, audio: torch.Tensor, null_audio: Optional[torch.Tensor],
@@ -87,6 +88,7 @@ class DenoiseEngine:
         with torch.cuda.graph(g):
             self._noise_static = self.unet.denoise_forward(self._x_static, self._t_static, rep=self.n_branch)
         self._graph, self._graph_key = g, key
+        self.captures += 1
 
     def unet_step(self, latents: torch.Tensor, t_dev: torch.Tensor) -> torch.Tensor:
         """noise prediction for the CFG batch; t_dev is a 1-element device f32 tensor."""

@@ -1436,6 +1436,28 @@ def guided_unipc(noise_pred: torch.Tensor, n_branch: int, g: float, x_in: torch.
           "avsd_guided_unipc")
 
 
+def window_turnover(x_prev: torch.Tensor, noise: torch.Tensor, x_next: Optional[torch.Tensor] = None, sigma: float = 1.0) -> torch.Tensor:
+    """avsd_window_turnover (include/avsd.h): x_next[:, :, 0] = x_prev[:, :, F-1] bit-exact, x_next[:, :, 1:] = noise * sigma, one launch.
+    x_prev, x_next (B, C, F, H, W) f32 contiguous, noise (B, C, F-1, H, W); x_next None or x_prev itself = in place."""
+    _req(x_prev, F32, "x_prev")
+    _req(noise, F32, "noise")
+    x_next = x_prev if x_next is None else x_next
+    _req(x_next, F32, "x_next")
+    if x_prev.dim() != 5 or not (x_prev.is_contiguous() and x_next.is_contiguous() and noise.is_contiguous()) or x_next.shape != x_prev.shape:
+        raise ValueError("window_turnover: contiguous x_prev / x_next of one shape (B, C, F, H, W)")
+    B, Cc, Fr, H, W = x_prev.shape
+    if tuple(noise.shape) != (B, Cc, Fr - 1, H, W) or not (x_next.device == x_prev.device == noise.device):
+        raise ValueError(f"window_turnover: noise must be {(B, Cc, Fr - 1, H, W)} on the latents' device, got {tuple(noise.shape)}")
+    nbytes = x_prev.numel() * 4
+    if x_next.data_ptr() != x_prev.data_ptr() and abs(x_next.data_ptr() - x_prev.data_ptr()) < nbytes:
+        raise ValueError("window_turnover: x_next must be x_prev itself or not overlap it")
+    if noise.data_ptr() < x_next.data_ptr() + nbytes and x_next.data_ptr() < noise.data_ptr() + noise.numel() * 4:
+        raise ValueError("window_turnover: noise must not overlap x_next")
+    check(_lib.lib().avsd_window_turnover(_p(x_prev), _p(noise) if noise.numel() else None, _p(x_next), float(sigma), B, Cc, Fr, H * W,
+                                          _stream()), "avsd_window_turnover")
+    return x_next
+
+
 def vae_postprocess(rows: torch.Tensor, n_img: int, H: int, W: int) -> torch.Tensor:
     _req(rows, P.ACT, "rows")
     out = torch.empty((n_img, 3, H, W), dtype=F32, device=rows.device)

@@ -200,11 +200,7 @@ class AudioCondAnimationPipeline:
 
         if self.use_engine and isinstance(self.scheduler, (PNDMScheduler, DDIMScheduler, DPMSolverMultistepScheduler,
                                                                UniPCMultistepScheduler)):
-            ekey = (id(self.unet), id(self.scheduler), float(audio_guidance_scale), float(text_guidance_scale))
-            if getattr(self, "_engine_key", None) != ekey:      # keep the engine (and its captured graph) across clips
-                self._engine = DenoiseEngine(self.unet, self.scheduler, audio_guidance_scale, text_guidance_scale)
-                self._engine_key = ekey
-            eng = self._engine
+            eng = self._engine_for(audio_guidance_scale, text_guidance_scale)
             self.unet.set_conditioning(text, audio, masks, video_length)      # already in the CFG branch order of :150-155,:186-194
             eng.prepare(latents, num_inference_steps)
             latents = latents.contiguous().clone()
@@ -224,6 +220,128 @@ class AudioCondAnimationPipeline:
         videos = self.decode_latents(latents.permute(0, 2, 1, 3, 4).reshape(b * f, c, h, w))
         videos = videos.reshape(b, f, *videos.shape[1:])
         return {"videos": videos} if return_dict else videos
+
+    def _engine_for(self, audio_guidance_scale: float, text_guidance_scale: float) -> DenoiseEngine:
+        ekey = (id(self.unet), id(self.scheduler), float(audio_guidance_scale), float(text_guidance_scale))
+        if getattr(self, "_engine_key", None) != ekey:      # keep the engine (and its captured graph) across clips
+            self._engine = DenoiseEngine(self.unet, self.scheduler, audio_guidance_scale, text_guidance_scale)
+            self._engine_key = ekey
+        return self._engine
+
+    # -- a whole audio track: chained windows -------------------------------------------------------------------------------
+    @torch.no_grad()
+    def pixel_handover_latents(self, frame_u8: torch.Tensor) -> torch.Tensor:
+        """(H, W, 3) uint8 device frame -> (1, 4, h, w) latents: what a by-hand chain through image files hands to the next window,
+        minus the JPEG loss.  The posterior's mode, not a sample, so that a track stays a function of (image, audio, seed)."""
+        img = (frame_u8.permute(2, 0, 1)[None].float() / 255.0) * 2.0 - 1.0
+        return self.vae.encode(img).latent_dist.mode() * self.vae.config.scaling_factor
+
+    @torch.no_grad()
+    def animate_track(self, image=None, audio=None, *, image_latents=None, text_encodings=None, texts=None, video_fps: int = 6,
+                      video_length: int = 12, height: int = 256, width: int = 256, num_inference_steps: int = 20,
+                      audio_guidance_scale: float = 4.0, text_guidance_scale: float = 1.0, generator=None, handover: str = "latent",
+                      output_type: str = "uint8", on_window: Optional[Callable] = None, sample_rate: int = 16000,
+                      audio_encodings=None, null_audio_encodings=None, audio_masks=None, n_samples: Optional[int] = None):
+        """Animates ONE still over a whole audio track: W chained windows of `video_length` = F frames (data_utils.track_windows).
+        Window 0 is `__call__` for one clip.  Window k > 0 starts from the last frame of window k-1, draws its F-1 noise frames from
+        the same `generator` (not re-seeded) and hears the audio that starts at its first frame's own time.
+
+        handover  "latent": frame 0 of window k is the finished latent of frame F-1 of window k-1, bit for bit (no VAE round trip);
+                  "pixel": that frame's decoded uint8 pixels are encoded again (`pixel_handover_latents`).
+        audio     (C, T) or (T,) waveform at `sample_rate`: resampled once, uploaded once (channel 0, which is what the mel front
+                  end reads), sliced on the device, and encoded through `encode_audio` in batches of at most 16 windows before the
+                  first denoising step.  Or `audio_encodings` (W, 229, D) [+ `null_audio_encodings` (1, 229, D), `audio_masks`],
+                  one row per window; `n_samples` then says how long the track is (default: W whole windows).
+        -> (n_frames, H, W, 3) uint8, on the host ("uint8") or on the device ("uint8_device"): window 0 gives F frames, every later
+        window its frames 1..F-1, and the tail that only the padding of the last window made is cut.  `on_window(k, frames_k)` sees
+        each window's share as it finishes.  One engine and one captured graph serve all windows (`DenoiseEngine.captures`); the
+        latents stay on the device from the first window to the last."""
+        from . import ops
+        from .data_utils import _resample, track_windows
+
+        device, f32, F = self.device, torch.float32, int(video_length)
+        if handover not in ("latent", "pixel"):
+            raise ValueError(f"animate_track: handover must be 'latent' or 'pixel', got {handover!r}")
+        if output_type not in ("uint8", "uint8_device"):
+            raise ValueError(f"animate_track: output_type must be 'uint8' or 'uint8_device', got {output_type!r}")
+        if not isinstance(self.scheduler, (PNDMScheduler, DDIMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler)):
+            raise ValueError(f"animate_track: runs on the DenoiseEngine, which has no plan for {type(self.scheduler).__name__}")
+        if image_latents is not None:
+            if image_latents.dim() == 3:
+                image_latents = image_latents[None]
+            if image_latents.dim() != 4 or image_latents.shape[0] != 1:
+                raise ValueError(f"animate_track: one track at a time: image_latents must be (4, h, w) or (1, 4, h, w), got "
+                                 f"{tuple(image_latents.shape)}; batched tracks are not supported")
+        do_text, do_audio = text_guidance_scale > 1.0, audio_guidance_scale > 1.0
+        k_cfg = 1 + int(do_text) + int(do_audio)
+
+        # -- the conditioning of every window, before the first denoising step
+        slices = None
+        if audio_encodings is None:
+            if audio is None:
+                raise ValueError("animate_track: pass audio= (a waveform) or audio_encodings= (one row per window)")
+            wave = torch.as_tensor(audio)
+            wave = _resample(wave[None] if wave.dim() == 1 else wave, int(sample_rate), 16000)[:1]
+            windows, W, n_frames, padded = track_windows(wave.shape[1], 16000, video_fps, F)
+            track = torch.zeros(1, padded, dtype=f32, device=device)
+            track[:, :wave.shape[1]] = wave.to(device=device, dtype=f32)                     # the one upload
+            win = F * 16000 // int(video_fps)
+            slices = [track[:, s:s + win] for s, _ in windows]
+        else:
+            W = audio_encodings.shape[0]
+            if n_samples is None:
+                n_frames = 1 + W * (F - 1)
+            else:
+                _, w_track, n_frames, _ = track_windows(n_samples, 16000, video_fps, F)
+                if w_track != W:
+                    raise ValueError(f"animate_track: a track of {n_samples} samples has {w_track} windows, audio_encodings has {W} rows")
+        text = self.encode_text(texts, device, f32, do_text, do_audio, text_encodings)                          # (k, 77, D), once
+        if text.shape[0] != k_cfg:
+            raise ValueError(f"animate_track: one track at a time: got text for {text.shape[0] / k_cfg:g} clips")
+        cond, masks = [], None
+        for j in range(0, W, 16):
+            n = min(16, W - j)
+            enc, masks = self.encode_audio(slices[j:j + n] if slices is not None else None, F, do_text, do_audio, device, f32,
+                                           audio_encodings=None if audio_encodings is None else audio_encodings[j:j + n],
+                                           null_audio_encodings=null_audio_encodings, audio_masks=audio_masks)
+            cond.append(enc.reshape(k_cfg, n, *enc.shape[1:]).transpose(0, 1))                                  # (n, k, 229, D)
+        cond = torch.cat(cond).contiguous()
+
+        if image_latents is None:
+            if image is None:
+                raise ValueError("animate_track: pass image= (needs a VAE encoder) or image_latents=")
+            image_latents = self.encode_latents(self._preprocess_images([image], height, width))
+        image_latents = image_latents.to(device=device, dtype=f32)
+        eng = self._engine_for(audio_guidance_scale, text_guidance_scale)
+        sigma = float(self.scheduler.init_noise_sigma)
+        mark = getattr(self, "_track_mark", None) or (lambda k, what: None)      # tools/track_bench.py: the phase boundaries of a window
+        out, x, frames = [], None, None
+        for k in range(W):
+            mark(k, "start")
+            if k == 0:                                                           # exactly the start of __call__ for one clip
+                x = self.prepare_video_latents(image_latents, self.unet.config.in_channels, F, height, width, device, f32,
+                                               generator).contiguous().clone()
+            else:
+                noise = torch.randn((1, x.shape[1], F - 1) + tuple(x.shape[3:]), generator=generator, device=device, dtype=f32)
+                ops.window_turnover(x, noise, x, sigma)                          # frame F-1 -> frame 0, fresh noise behind it
+                if handover == "pixel":
+                    x[:, :, 0] = self.pixel_handover_latents(frames[F - 1]) * sigma
+            self.unet.set_conditioning(text, cond[k], masks, F)                  # same shapes: refreshed in place, the graph stays
+            eng.prepare(x, num_inference_steps)
+            mark(k, "denoise")
+            for i in self.progress_bar(range(self.scheduler.num_forwards())):
+                eng.step(x, i)
+            mark(k, "decode")
+            frames = self.vae.decode_to_uint8_frames(x)[0]                        # (F, H, W, 3) on the device
+            first = k * (F - 1) + (1 if k else 0)                                # index of this window's first NEW output frame
+            piece = frames[(1 if k else 0):][:max(0, n_frames - first)]
+            if output_type == "uint8":
+                piece = piece.cpu()
+            mark(k, "end")
+            out.append(piece)
+            if on_window is not None:
+                on_window(k, piece)
+        return torch.cat(out)
 
     def _reference_style_loop(self, latents, text, audio, masks, video_length, steps, do_text, do_audio, ag, tg):
         """The loop exactly as the reference writes it (:325-365): torch.cat duplication, unet(...).sample,
@@ -365,6 +483,52 @@ def generate_videos(pipeline, image_path: str = "", audio_path: str = "", video_
     if save_template:
         return None
     return videos, audios_out
+
+
+@torch.no_grad()
+def generate_track(pipeline, image_path: str = "", audio_path: str = "", video_path: str = "", category: str = "",
+                   category_text_encoding: Optional[torch.Tensor] = None, image_size: Tuple[int, int] = (256, 256),
+                   video_fps: int = 6, video_num_frame: int = 12, audio_guidance_scale: float = 4.0, text_guidance_scale: float = 1.0,
+                   seed: int = 0, save_path: str = "", device: torch.device = torch.device("cuda"), *, handover: str = "latent",
+                   writer: Optional[Callable] = None):
+    """`generate_videos` for a whole track: ONE video as long as the audio (AudioCondAnimationPipeline.animate_track) instead of
+    `num_clips_per_video` separate windows of it.  The still is `image_path`, or the first frame of `video_path`; the audio is
+    `audio_path`, or the audio track of `video_path`.  With `save_path` one file is written through `write_video` (the frames, and
+    the audio cut to their duration) and its name returned; otherwise -> (frames (n, H, W, 3) uint8 on the host, audio (1, T) at 16 kHz).
+    **No trained checkpoint has been run through this: what many chained windows do to the picture (drift) is unmeasured.**"""
+    from .data_utils import _load_audio_file, _open_video, _resample, load_and_transform_images_stable_diffusion
+    from .video_io import get_jpeg_encoder
+
+    if not (image_path or video_path) or not (audio_path or video_path):
+        raise ValueError("generate_track: needs image_path and audio_path, or video_path for whichever of the two is missing")
+    src = _open_video(video_path) if video_path else None
+    if image_path:
+        image = load_image(image_path, image_size)
+    else:
+        first = src.video_clip(0.0, 1.0 / video_fps, video_fps, 1)                                 # (1, 3, h, w) in [0, 1]
+        image = load_and_transform_images_stable_diffusion(first, size=image_size, normalize=False).float()[0]
+    if audio_path:
+        audio, sr = _load_audio_file(audio_path)
+        audio = _resample(audio, sr, 16000)
+    else:
+        if getattr(src, "audio", True) is None:
+            raise ValueError(f"generate_track: {video_path} has no audio track; pass audio_path")
+        audio = src.audio_clip(0.0, src.audio_duration)                                            # resampled to 16 kHz
+    audio = audio[:1].contiguous()
+    generator = torch.Generator(device=device)
+    generator.manual_seed(seed)
+    on_device = bool(save_path) and get_jpeg_encoder() == "device"
+    frames = pipeline.animate_track(image, audio, texts=[category],
+                                    text_encodings=[category_text_encoding] if category_text_encoding is not None else None,
+                                    video_fps=video_fps, video_length=video_num_frame, height=image_size[0], width=image_size[1],
+                                    num_inference_steps=getattr(pipeline, "generation_steps", 50),
+                                    audio_guidance_scale=audio_guidance_scale, text_guidance_scale=text_guidance_scale,
+                                    generator=generator, handover=handover, output_type="uint8_device" if on_device else "uint8")
+    audio = audio[:, :frames.shape[0] * 16000 // video_fps]            # the track itself, or its padding cut to the frames' duration
+    if not save_path:
+        return frames, audio
+    os.makedirs(os.path.dirname(save_path) or ".", exist_ok=True)
+    return (writer or write_video)(save_path, frames, video_fps, audio, 16000, "aac")
 
 
 @torch.no_grad()

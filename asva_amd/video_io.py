@@ -161,10 +161,8 @@ def encode_jpeg_frames(frames, quality: int = 95) -> List[bytes]:
 _warned_size = False
 
 
-def write_mjpeg_avi(filename: str, video_array, fps: float, audio_array=None, audio_fps: int = 16000, quality: int = 95,
-                    encoder: Optional[str] = None) -> str:
-    """`encoder`: "host" (PIL) or "device" (`encode_jpeg_frames`); None = the `set_jpeg_encoder` setting.  "device" uploads a host
-    array first, needs a GPU, and leaves frames whose H or W is no multiple of 8 to PIL (with one warning)."""
+def _encode_mjpeg_frames(video_array, quality: int, encoder: Optional[str]) -> Tuple[List[bytes], int, int]:
+    """uint8 (T, H, W, 3) frames -> (T complete JPEG files, H, W), by PIL or on the device (see `write_mjpeg_avi`)"""
     global _warned_size
     mode = _jpeg_encoder if encoder is None else encoder
     if mode not in _JPEG_ENCODERS:
@@ -179,7 +177,7 @@ def write_mjpeg_avi(filename: str, video_array, fps: float, audio_array=None, au
         if H % 8 or W % 8:
             if not _warned_size:
                 warnings.warn(f"write_mjpeg_avi: the device JPEG encoder takes frames whose height and width are multiples of 8, got "
-                              f"{H} x {W}: PIL encodes these (4:2:0)", RuntimeWarning, stacklevel=2)
+                              f"{H} x {W}: PIL encodes these (4:2:0)", RuntimeWarning, stacklevel=3)
                 _warned_size = True
         else:
             frames = encode_jpeg_frames(v, quality)
@@ -194,15 +192,22 @@ def write_mjpeg_avi(filename: str, video_array, fps: float, audio_array=None, au
             buf = io.BytesIO()
             Image.fromarray(video[t]).save(buf, format="JPEG", quality=quality)
             frames.append(buf.getvalue())
-    pcm, nch = b"", 0
-    if audio_array is not None:
-        a = audio_array.detach().cpu().numpy() if torch.is_tensor(audio_array) else np.asarray(audio_array)
-        if a.ndim == 1:
-            a = a[None]
-        nch = a.shape[0]
-        pcm = (np.clip(a.T.astype(np.float64), -1.0, 1.0) * 32767.0).round().astype("<i2").tobytes()      # interleaved
+    return frames, H, W
+
+
+def _pcm16(audio_array) -> Tuple[bytes, int]:
+    """(C, Ta) or (Ta,) float waveform in [-1, 1] -> (interleaved 16-bit PCM, channels); None -> (b"", 0)"""
+    if audio_array is None:
+        return b"", 0
+    a = audio_array.detach().cpu().numpy() if torch.is_tensor(audio_array) else np.asarray(audio_array)
+    if a.ndim == 1:
+        a = a[None]
+    return (np.clip(a.T.astype(np.float64), -1.0, 1.0) * 32767.0).round().astype("<i2").tobytes(), a.shape[0]
+
+
+def _avi_hdrl(fps: float, T: int, H: int, W: int, max_frame: int, nch: int, audio_fps: int, pcm_bytes: int) -> bytes:
+    """payload of the `hdrl` list: main header, the MJPG stream and, with nch > 0, the PCM stream"""
     rate, scale = int(round(fps * 1000)), 1000
-    max_frame = max(len(f) for f in frames)
     streams = 1 + (1 if nch else 0)
     avih = struct.pack("<14I", int(round(1e6 / fps)), 0, 0, 0x10, T, 0, streams, max_frame, W, H, 0, 0, 0, 0)
     strh_v = struct.pack("<4s4sIHHIIIIIIII4h", b"vids", b"MJPG", 0, 0, 0, 0, scale, rate, 0, T, max_frame, 0xFFFFFFFF, 0, 0, 0, W, H)
@@ -210,11 +215,23 @@ def write_mjpeg_avi(filename: str, video_array, fps: float, audio_array=None, au
     hdrl = _chunk(b"avih", avih) + _list(b"strl", _chunk(b"strh", strh_v) + _chunk(b"strf", strf_v))
     if nch:
         align = 2 * nch
-        nsamp = len(pcm) // align
-        strh_a = struct.pack("<4s4sIHHIIIIIIII4h", b"auds", b"\0\0\0\0", 0, 0, 0, 0, align, audio_fps * align, 0, nsamp, len(pcm), 0xFFFFFFFF,
+        nsamp = pcm_bytes // align
+        strh_a = struct.pack("<4s4sIHHIIIIIIII4h", b"auds", b"\0\0\0\0", 0, 0, 0, 0, align, audio_fps * align, 0, nsamp, pcm_bytes, 0xFFFFFFFF,
                              align, 0, 0, 0, 0)
         strf_a = struct.pack("<HHIIHHH", 1, nch, audio_fps, audio_fps * align, align, 16, 0)
         hdrl += _list(b"strl", _chunk(b"strh", strh_a) + _chunk(b"strf", strf_a))
+    return hdrl
+
+
+def write_mjpeg_avi(filename: str, video_array, fps: float, audio_array=None, audio_fps: int = 16000, quality: int = 95,
+                    encoder: Optional[str] = None) -> str:
+    """`encoder`: "host" (PIL) or "device" (`encode_jpeg_frames`); None = the `set_jpeg_encoder` setting.  "device" uploads a host
+    array first, needs a GPU, and leaves frames whose H or W is no multiple of 8 to PIL (with one warning)."""
+    frames, H, W = _encode_mjpeg_frames(video_array, quality, encoder)
+    T = len(frames)
+    pcm, nch = _pcm16(audio_array)
+    max_frame = max(len(f) for f in frames)
+    hdrl = _avi_hdrl(fps, T, H, W, max_frame, nch, audio_fps, len(pcm))
     movi, index, off = b"", b"", 4
     items = [(b"00dc", f) for f in frames] + ([(b"01wb", pcm)] if nch else [])
     for tag, data in items:
@@ -226,6 +243,82 @@ def write_mjpeg_avi(filename: str, video_array, fps: float, audio_array=None, au
     with open(filename, "wb") as f:
         f.write(b"RIFF" + struct.pack("<I", len(body)) + body)
     return filename
+
+
+class MjpegAviWriter:
+    """`write_mjpeg_avi` for videos that arrive in pieces (AudioCondAnimationPipeline.animate_track's windows): `append` encodes
+    and writes a piece's frames at once, so a long track never holds more than one piece; `close(audio)` writes the audio chunk
+    and the index, then goes back and fills in the headers (frame count, largest frame, audio length), which is all it kept.
+
+        w = MjpegAviWriter(path, fps, (H, W), audio_fps)
+        w.append(frames_0); w.append(frames_1); ...          # uint8 (T_i, H, W, 3), host or device
+        w.close(audio)                                       # (C, Ta) float waveform or None
+
+    The file is what `read_mjpeg_avi` / `walk_mjpeg_avi` read.  It differs from `write_mjpeg_avi`'s bytes for the same content in
+    one place: room for the audio stream's header is set aside before the first frame, and a file closed without audio carries
+    a JUNK chunk there instead.  `encoder`: as `write_mjpeg_avi`."""
+
+    def __init__(self, path: str, fps: float, size: Tuple[int, int], audio_fps: int = 16000, quality: int = 95,
+                 encoder: Optional[str] = None):
+        self.path, self.fps, (self.H, self.W), self.audio_fps = path, float(fps), (int(size[0]), int(size[1])), int(audio_fps)
+        self.quality, self.encoder = quality, encoder
+        self.n_frames, self._max_frame, self._index = 0, 0, []
+        self._room = len(_list(b"hdrl", _avi_hdrl(self.fps, 0, self.H, self.W, 0, 1, self.audio_fps, 0)))
+        self._f = open(path, "wb")
+        self._f.write(b"\0" * (12 + self._room) + b"LIST\0\0\0\0movi")
+        self._off = 4                                     # of the next chunk, from the `movi` tag (what idx1 counts from)
+
+    def _put(self, tag: bytes, data: bytes) -> None:
+        self._index.append(struct.pack("<4sIII", tag, 0x10, self._off, len(data)))
+        c = _chunk(tag, data)
+        self._f.write(c)
+        self._off += len(c)
+
+    def append(self, frames) -> int:
+        """uint8 (T, H, W, 3) frames (host array, host or device tensor) -> the number of frames in the file so far"""
+        if self._f is None:
+            raise ValueError("MjpegAviWriter.append: the file is closed")
+        if tuple(frames.shape[1:]) != (self.H, self.W, 3):
+            raise ValueError(f"MjpegAviWriter.append: frames must be (T, {self.H}, {self.W}, 3), got {tuple(frames.shape)}")
+        jpegs, _, _ = _encode_mjpeg_frames(frames, self.quality, self.encoder)
+        for j in jpegs:
+            self._put(b"00dc", j)
+            self._max_frame = max(self._max_frame, len(j))
+        self.n_frames += len(jpegs)
+        return self.n_frames
+
+    def close(self, audio=None) -> str:
+        if self._f is None:
+            return self.path
+        if self.n_frames == 0:
+            self._f.close()
+            self._f = None
+            raise ValueError("MjpegAviWriter.close: no frames were appended")
+        pcm, nch = _pcm16(audio)
+        if nch:
+            self._put(b"01wb", pcm)
+        movi_bytes = self._off                            # `movi` tag + chunks
+        self._f.write(_chunk(b"idx1", b"".join(self._index)))
+        total = self._f.tell()
+        head = _list(b"hdrl", _avi_hdrl(self.fps, self.n_frames, self.H, self.W, self._max_frame, nch, self.audio_fps, len(pcm)))
+        if len(head) < self._room:
+            head += _chunk(b"JUNK", b"\0" * (self._room - len(head) - 8))
+        assert len(head) == self._room
+        self._f.seek(0)
+        self._f.write(b"RIFF" + struct.pack("<I", total - 8) + b"AVI " + head + b"LIST" + struct.pack("<I", movi_bytes))
+        self._f.close()
+        self._f = None
+        return self.path
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        elif self._f is not None:
+            self._f.close()
+            self._f = None
 
 
 # ---- where the frames are decoded ----------------------------------------------------------------------------------------

@@ -429,6 +429,15 @@ int avsd_guided_unipc(const float* noise_pred, int n_branch, float g, float g2, 
                       float cc_last, float cc_cur, float cp_x, float cp_cur, int B, int C, int F, int HW,
                       void* stream);
 
+/* Turnover between two chained windows of a long track (asva_amd/pipeline.py animate_track) on (B, C, F, H, W) f32 latents:
+ *   x_next[:, :, 0]  = x_prev[:, :, F-1]      (bit-exact: the last finished frame conditions the next window)
+ *   x_next[:, :, 1:] = noise * sigma          (noise (B, C, F-1, H, W) f32; sigma = the scheduler's init_noise_sigma)
+ * x_next == x_prev (in place) is allowed: frame F-1 is read before frame 0 and frame F-1 are written.  x_next may otherwise
+ * not overlap x_prev, and noise may not overlap x_next (AVSD_EINVAL).  Pointers need 4-byte alignment only; noise may be
+ * NULL when F == 1.  One launch. */
+int avsd_window_turnover(const float* x_prev, const float* noise, float* x_next, float sigma, int B, int C, int F, int HW,
+                         void* stream);
+
 /* VAE post-processing (pipeline_audio_cond_animation.py:212): channels-last bf16
  * [N*H*W][ld] (3 channels) -> (N, 3, H, W) f32 = clamp(x / 2 + 0.5, 0, 1). */
 int avsd_vae_postprocess(const void* src, int ld, float* dst, int N, int HW, void* stream);
