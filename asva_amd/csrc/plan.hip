@@ -93,6 +93,8 @@ const Entry kEntries[] = {
     AVSD_PLAN_ENTRY(avsd_jpeg_quantize_u8), AVSD_PLAN_ENTRY(avsd_jpeg_pack_i16),
     // baseline JPEG decoder (csrc/jpeg.hip)
     AVSD_PLAN_ENTRY(avsd_jpeg_decode_scan), AVSD_PLAN_ENTRY(avsd_jpeg_idct_rgb_u8),
+    // denoising loss (csrc/loss.hip)
+    AVSD_PLAN_ENTRY(avsd_diffuse_clip_f32), AVSD_PLAN_ENTRY(avsd_frame_mse_f32),
 };
 
 struct Reloc {

@@ -1458,6 +1458,81 @@ def window_turnover(x_prev: torch.Tensor, noise: torch.Tensor, x_next: Optional[
     return x_next
 
 
+FRAME_MSE_PARTS = 64     # AVSD_FRAME_MSE_PARTS (include/avsd.h): avsd_frame_mse_f32 wants B * FRAME_MSE_PARTS floats of scratch
+DIFFUSE_MODES = {"epsilon": 0, "v": 1, "v_prediction": 1}
+
+
+def _apart(a: torch.Tensor, b: torch.Tensor) -> bool:
+    pa, pb = a.data_ptr(), b.data_ptr()
+    return pa + a.numel() * a.element_size() <= pb or pb + b.numel() * b.element_size() <= pa
+
+
+def check_timesteps(timesteps: torch.Tensor, n: int, T: int, device) -> torch.Tensor:
+    """(n,) integer timesteps, all in [0, T) -> int32 vector on `device`.  Raises instead of clamping; a CPU tensor is checked on
+    the host, a device tensor with one min / max read-back."""
+    if timesteps.dim() != 1 or timesteps.numel() != n or timesteps.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"timesteps: expected an int32 / int64 vector of {n} entries, got {timesteps.dtype} {tuple(timesteps.shape)}")
+    lo, hi = (int(v) for v in torch.aminmax(timesteps))
+    if lo < 0 or hi >= T:
+        raise ValueError(f"timesteps: [{lo}, {hi}] leaves the table's range [0, {T})")
+    return timesteps.to(device=device, dtype=torch.int32).contiguous()
+
+
+def diffuse_clip(x0: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor, sqrt_acp: torch.Tensor, sqrt_1m_acp: torch.Tensor,
+                 keep_first: bool = True, mode: str = "epsilon", want_target: bool = True, noisy: Optional[torch.Tensor] = None,
+                 target: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """avsd_diffuse_clip_f32 (include/avsd.h), one launch on contiguous (B, C, F, H, W) f32: noisy = a x0 + s noise with frame 0 kept
+    bit-exact when keep_first, target = noise (epsilon) or a noise - s x0 (v).  -> (noisy, target); target is None unless wanted.
+    timesteps: (B,) integers, validated against the tables' length here (ValueError), on any device."""
+    if mode not in DIFFUSE_MODES:
+        raise ValueError(f"diffuse_clip: mode must be one of {sorted(DIFFUSE_MODES)}, got {mode!r}")
+    _req(x0, F32, "x0")
+    _req(noise, F32, "noise")
+    _req(sqrt_acp, F32, "sqrt_acp")
+    _req(sqrt_1m_acp, F32, "sqrt_1m_acp")
+    if x0.dim() != 5 or x0.numel() == 0 or noise.shape != x0.shape or not (x0.is_contiguous() and noise.is_contiguous()):
+        raise ValueError("diffuse_clip: contiguous non-empty x0 / noise of one shape (B, C, F, H, W)")
+    T = sqrt_acp.numel()
+    if T == 0 or sqrt_acp.dim() != 1 or sqrt_1m_acp.shape != sqrt_acp.shape or not (sqrt_acp.device == sqrt_1m_acp.device == x0.device == noise.device):
+        raise ValueError("diffuse_clip: two f32 tables of one length on the latents' device")
+    B, Cc, Fr, H, W = x0.shape
+    ts = check_timesteps(timesteps, B, T, x0.device)
+    noisy = torch.empty_like(x0) if noisy is None else noisy
+    if want_target and target is None:
+        target = torch.empty_like(x0)
+    outs = [noisy] + ([target] if target is not None else [])
+    for o in outs:
+        _req(o, F32, "output")
+        if o.shape != x0.shape or not o.is_contiguous() or o.device != x0.device:
+            raise ValueError("diffuse_clip: outputs must be contiguous with x0's shape on its device")
+        if not all(_apart(o, i) for i in (x0, noise, ts, sqrt_acp, sqrt_1m_acp)):
+            raise ValueError("diffuse_clip: an output overlaps an input (noisy may not be x0)")
+    if target is not None and not _apart(noisy, target):
+        raise ValueError("diffuse_clip: noisy and target overlap")
+    check(_lib.lib().avsd_diffuse_clip_f32(_p(x0), _p(noise), _p(ts), _p(sqrt_acp), _p(sqrt_1m_acp), T, _p(noisy), _p(target),
+                                           int(bool(keep_first)), DIFFUSE_MODES[mode], B, Cc, Fr, H * W, _stream()), "avsd_diffuse_clip_f32")
+    return noisy, target
+
+
+def frame_mse(pred: torch.Tensor, target: torch.Tensor, first_frame: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """avsd_frame_mse_f32 (include/avsd.h) on contiguous (B, C, F, H, W) f32 -> (loss 0-dim, per_sample (B,)): the mean squared
+    difference over frames first_frame.. per sample, and its batch mean (= F.mse_loss of the sliced tensors).  Deterministic;
+    per_sample[b] depends neither on B nor on b."""
+    _req(pred, F32, "pred")
+    _req(target, F32, "target")
+    if pred.dim() != 5 or pred.numel() == 0 or target.shape != pred.shape or not (pred.is_contiguous() and target.is_contiguous()) or pred.device != target.device:
+        raise ValueError("frame_mse: contiguous non-empty pred / target of one shape (B, C, F, H, W) on one device")
+    B, Cc, Fr, H, W = pred.shape
+    f0 = int(first_frame)
+    if not 0 <= f0 < Fr:
+        raise ValueError(f"frame_mse: no frames to score: first_frame {f0} of {Fr}")
+    scratch = torch.empty((B * FRAME_MSE_PARTS + B + 1,), dtype=F32, device=pred.device)
+    per_sample, loss = scratch[B * FRAME_MSE_PARTS:B * FRAME_MSE_PARTS + B], scratch[B * FRAME_MSE_PARTS + B:]
+    check(_lib.lib().avsd_frame_mse_f32(_p(pred), _p(target), f0, _p(scratch), _p(per_sample), _p(loss), B, Cc, Fr, H * W, _stream()),
+          "avsd_frame_mse_f32")
+    return loss.reshape(()), per_sample
+
+
 def vae_postprocess(rows: torch.Tensor, n_img: int, H: int, W: int) -> torch.Tensor:
     _req(rows, P.ACT, "rows")
     out = torch.empty((n_img, 3, H, W), dtype=F32, device=rows.device)

@@ -438,6 +438,34 @@ int avsd_guided_unipc(const float* noise_pred, int n_branch, float g, float g2, 
 int avsd_window_turnover(const float* x_prev, const float* noise, float* x_next, float sigma, int B, int C, int F, int HW,
                          void* stream);
 
+/* ---- the training objective's forward value (asva_amd/trainer.py; kernels in csrc/loss.hip): f32 and integers in both builds ----
+ * Noising step of audio_cond_animation_trainer.py:119-134 on contiguous (B, C, F, H, W) f32 tensors, one launch.  For sample b
+ * with t = timesteps[b] (device int32), a = sqrt_acp[t], s = sqrt_1m_acp[t] (device f32 tables of T entries):
+ *   noisy[b, :, f]  = x0[b, :, f]                 bit-exact, when keep_first and f == 0  (the trainer's first-frame splice)
+ *                   = fma(a, x0, s * noise)       otherwise                              (scheduler.add_noise)
+ *   target[b]       = noise[b]                    bit-exact, every frame, mode AVSD_DIFFUSE_EPSILON
+ *                   = fma(a, noise, -(s * x0))    mode AVSD_DIFFUSE_V                    (scheduler.get_velocity)
+ * target may be NULL (the caller uses noise itself, or wants add_noise only).  A sample whose timestep lies outside [0, T) is
+ * left untouched: nothing of noisy[b] / target[b] is written and the tables are not read (asva_amd/ops.py validates the vector
+ * and raises).  Pointers need 4-byte alignment only.  An output that overlaps an input or the other output is AVSD_EINVAL;
+ * noisy == x0 is not allowed. */
+#define AVSD_DIFFUSE_EPSILON 0
+#define AVSD_DIFFUSE_V 1
+int avsd_diffuse_clip_f32(const float* x0, const float* noise, const int32_t* timesteps, const float* sqrt_acp,
+                          const float* sqrt_1m_acp, int T, float* noisy, float* target, int keep_first, int mode, int B, int C,
+                          int F, int HW, void* stream);
+/* Denoising loss on (B, C, F, H, W) f32 tensors (audio_cond_animation_trainer.py:145-148):
+ *   per_sample[b] = mean((pred - target)[b, :, f0:]^2)        n = C * (F - f0) * HW terms
+ *   loss[0]       = mean_b per_sample[b]                      = F.mse_loss on the sliced tensors (every sample has n terms)
+ * f0 = 1 is the reference's default, 0 its loss_on_first_frame; 0 <= f0 < F.  Deterministic, no atomics, two launches: each
+ * sample is cut into AVSD_FRAME_MSE_PARTS fixed pieces (by n alone), a workgroup folds its piece in f32 in a fixed tree and
+ * writes scratch[b * AVSD_FRAME_MSE_PARTS + part]; the second launch folds a sample's partials in double in a fixed tree,
+ * then the samples in index order.  per_sample[b] therefore depends neither on B nor on b.  scratch: B *
+ * AVSD_FRAME_MSE_PARTS floats, caller-provided, overwritten.  Pointers need 4-byte alignment only. */
+#define AVSD_FRAME_MSE_PARTS 64
+int avsd_frame_mse_f32(const float* pred, const float* target, int f0, float* scratch, float* per_sample, float* loss, int B, int C,
+                       int F, int HW, void* stream);
+
 /* VAE post-processing (pipeline_audio_cond_animation.py:212): channels-last bf16
  * [N*H*W][ld] (3 channels) -> (N, 3, H, W) f32 = clamp(x / 2 + 0.5, 0, 1). */
 int avsd_vae_postprocess(const void* src, int ld, float* dst, int N, int HW, void* stream);
