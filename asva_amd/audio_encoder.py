@@ -23,9 +23,7 @@ the appended pair; its query/output are computed and never read.
 """
 from __future__ import annotations
 
-import json
 import math
-import os
 from typing import Any, Dict, Optional
 
 import torch
@@ -33,9 +31,9 @@ import torch
 from . import precision as P
 import torch.nn as nn
 
-from . import ops
+from . import modelio, ops
 from .conditioning import audio_segment_mask
-from .unet import BIN_NAME, CONFIG_NAME, SAFETENSORS_NAME, FrozenConfig
+from .unet import FrozenConfig
 
 EMBED, HEADS, DEPTH, MLP, OUT_DIM = 768, 12, 12, 3072, 1024
 MEL, FRAMES, PATCH, STRIDE = 128, 204, 16, 10
@@ -115,8 +113,8 @@ class _Trunk(nn.Module):
         self.blocks = nn.ModuleList([_BlockP() for _ in range(DEPTH)])
 
 
-class ImageBindSegmaskAudioEncoder(nn.Module):
-    config_name = CONFIG_NAME
+class ImageBindSegmaskAudioEncoder(modelio.Invalidating, nn.Module):
+    config_name = modelio.CONFIG_NAME
 
     IMAGEBIND_CKPT = ".checkpoints/imagebind_huge.pth"      # where imagebind_huge(pretrained=True) keeps its weights
 
@@ -170,16 +168,8 @@ class ImageBindSegmaskAudioEncoder(nn.Module):
 
     @classmethod
     def from_pretrained(cls, pretrained_model_path: str, subfolder: Optional[str] = None, **kw):
-        path = os.path.join(pretrained_model_path, subfolder) if subfolder else pretrained_model_path
-        with open(os.path.join(path, CONFIG_NAME)) as f:
-            model = cls.from_config(json.load(f), **kw)
-        st = os.path.join(path, SAFETENSORS_NAME)
-        if os.path.isfile(st):
-            from safetensors.torch import load_file
-
-            sd = load_file(st)
-        else:
-            sd = torch.load(os.path.join(path, BIN_NAME), map_location="cpu", weights_only=True)
+        model = cls.from_config(modelio.read_config(pretrained_model_path, subfolder), **kw)
+        sd = modelio.read_state_dict(pretrained_model_path, subfolder)
         own = model.state_dict()
         # the checkpoint holds all of ImageBind's audio modules; anything outside the restated subset is reported
         missing = [k for k in own if k not in sd]
@@ -189,28 +179,10 @@ class ImageBindSegmaskAudioEncoder(nn.Module):
         return model.eval()
 
     def save_pretrained(self, save_directory: str, safe_serialization: bool = True):
-        os.makedirs(save_directory, exist_ok=True)
-        cfg = {"_class_name": type(self).__name__, "_diffusers_version": "0.29.2"}
-        cfg.update(self.config)
-        with open(os.path.join(save_directory, CONFIG_NAME), "w") as f:
-            json.dump(cfg, f, indent=2)
-        sd = {k: v.detach().cpu().contiguous() for k, v in self.state_dict().items()}
-        if safe_serialization:
-            from safetensors.torch import save_file
+        modelio.write_folder(save_directory, modelio.diffusers_config(self, self.config), self.state_dict(), safe_serialization)
 
-            save_file(sd, os.path.join(save_directory, SAFETENSORS_NAME))
-        else:
-            torch.save(sd, os.path.join(save_directory, BIN_NAME))
-
-    def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        r = super().load_state_dict(state_dict, strict=strict, **kw)
+    def _invalidate(self) -> None:
         self._packed = None
-        return r
-
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        self._packed = None
-        return r
 
     @property
     def device(self):

@@ -14,7 +14,6 @@ seeded weights (tests/golden/avsync_tiny.pt), and no RelSync value of a real cli
 """
 from __future__ import annotations
 
-import json
 import os
 from typing import Dict, Optional
 
@@ -22,12 +21,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import f32net, ops
+from . import f32net, modelio, ops
 from .weights import _Pk
 
-CONFIG_NAME = "config.json"
-BIN_NAME = "diffusion_pytorch_model.bin"
-SAFETENSORS_NAME = "diffusion_pytorch_model.safetensors"
 DEFAULT_MODEL_PATH = "checkpoints/avsync/vggss_sync_contrast/ckpts/checkpoint-40000/modules"
 AVID_CMA_CHECKPOINT = "./pretrained/AVID-CMA_Audioset_InstX-N1024-PosW-N64-Top32_checkpoint.pth.tar"
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
@@ -36,8 +32,9 @@ INPUT_SIZE = 224
 
 
 # ---- parameter holders -----------------------------------------------------------------------------------------------------------
-class _Pretrained(nn.Module):
-    """config + diffusers directory layout (config.json + diffusion_pytorch_model.bin / .safetensors) for the three sub-networks"""
+class _Pretrained(modelio.EpochCounted, nn.Module):
+    """config + diffusers directory layout (config.json + diffusion_pytorch_model.bin / .safetensors) for the three sub-networks;
+    `_epoch` counts the changes of the parameters: the packed weights of the enclosing classifier follow every one"""
 
     _config: Dict
 
@@ -51,48 +48,16 @@ class _Pretrained(nn.Module):
 
     @classmethod
     def from_pretrained(cls, pretrained_model_path: str, subfolder: Optional[str] = None, use_safetensors: Optional[bool] = None, **_):
-        path = os.path.join(pretrained_model_path, subfolder) if subfolder else pretrained_model_path
-        with open(os.path.join(path, CONFIG_NAME)) as f:
-            cfg = {k: v for k, v in json.load(f).items() if not k.startswith("_")}
-        model = cls(**cfg)
-        st, bn = os.path.join(path, SAFETENSORS_NAME), os.path.join(path, BIN_NAME)
-        if use_safetensors is not False and os.path.isfile(st):
-            from safetensors.torch import load_file
-
-            sd = load_file(st)
-        elif os.path.isfile(bn):
-            sd = torch.load(bn, map_location="cpu", weights_only=True)
-        else:
-            raise FileNotFoundError(f"no {BIN_NAME}" + ("" if use_safetensors is False else f" or {SAFETENSORS_NAME}") + f" under {path}")
-        model.load_state_dict(sd)
+        model = cls(**modelio.read_config(pretrained_model_path, subfolder, drop_private=True))
+        model.load_state_dict(modelio.read_state_dict(pretrained_model_path, subfolder, use_safetensors=use_safetensors))
         return model.eval()
 
     def save_pretrained(self, save_directory: str, safe_serialization: bool = False):
-        os.makedirs(save_directory, exist_ok=True)
-        with open(os.path.join(save_directory, CONFIG_NAME), "w") as f:
-            json.dump({"_class_name": type(self).__name__, **self._config}, f, indent=2)
-        sd = {k: v.detach().cpu().contiguous() for k, v in self.state_dict().items()}
-        if safe_serialization:
-            from safetensors.torch import save_file
-
-            save_file(sd, os.path.join(save_directory, SAFETENSORS_NAME))
-        else:
-            torch.save(sd, os.path.join(save_directory, BIN_NAME))
+        modelio.write_folder(save_directory, {"_class_name": type(self).__name__, **self._config}, self.state_dict(), safe_serialization)
 
     def _load_avid_cma(self, prefix: str):
         sd = torch.load(AVID_CMA_CHECKPOINT, map_location="cpu")["model"]
         self.load_state_dict({k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)})
-
-    # the packed weights of the enclosing classifier follow every change of the parameters
-    def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        r = super().load_state_dict(state_dict, strict=strict, **kw)
-        self._epoch = getattr(self, "_epoch", 0) + 1
-        return r
-
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        self._epoch = getattr(self, "_epoch", 0) + 1
-        return r
 
 
 def _conv_bn3d(cin, cout, k, stride, pad):
@@ -276,13 +241,10 @@ class AVSyncClassifier(f32net.F32Net):
     # real torch modules underneath: nn.Module's own loader and .to(); a sub-network loaded or moved on its own counts too
     to = nn.Module.to
 
-    def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        r = nn.Module.load_state_dict(self, state_dict, strict=strict, **kw)
-        self._epoch += 1
-        return r
+    load_state_dict = modelio.EpochCounted.load_state_dict
 
     def _pack_epoch(self) -> int:
-        return self._epoch + sum(getattr(m, "_epoch", 0) for m in (self.audio_encoder, self.video_encoder, self.head))
+        return self._epoch + sum(m._epoch for m in (self.audio_encoder, self.video_encoder, self.head))
 
     def _fold(self, state_dict) -> _Pk:
         for m in self.modules():

@@ -1,6 +1,7 @@
-"""What the on-device f32 metric networks share (fid.py, fvd.py, avsync.py, imagebind_eval.py): a parameter holder built from a table of
-state-dict shapes, its checked loader, the cached pack into ONE weights.Blob, the float64 BatchNorm fold with the re-layout to
-[cout][taps][cin] that the f32 convolution kernels read, and the launches every one of them uses.  Host-side only: no kernel lives here.
+"""What the on-device f32 networks share (fid.py, fvd.py, avsync.py, imagebind_eval.py, text_encoder.py): a parameter holder built from a
+table of state-dict shapes, its checked loader, the cached pack into ONE weights.Blob, the float64 BatchNorm fold with the re-layout to
+[cout][taps][cin] that the f32 convolution kernels read, the launches every one of them uses, and the pre-LN transformer blocks as a
+sequence of those launches (`run_blocks`).  Host-side only: no kernel lives here.
 """
 from __future__ import annotations
 
@@ -11,6 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .modelio import EpochCounted
 from .weights import Blob, _Pk, pack_device
 
 
@@ -31,16 +33,16 @@ def declare(module: nn.Module, shapes: Dict[str, Sequence[int]]) -> None:
             mod.register_parameter(parts[-1], nn.Parameter(torch.empty(shape, dtype=torch.float32), requires_grad=False))
 
 
-class F32Net(nn.Module):
+class F32Net(EpochCounted, nn.Module):
     """A network that computes in f32 only, from weights that `_fold` lays out for the kernels and `pack` keeps in one device blob.
     `_epoch` counts the changes of the parameters (load_state_dict, .to()): a pack made under another count is stale."""
 
     STRICT_KEYS = True      # load_state_dict(strict=True) refuses tensors the model does not have
+    ANY_DTYPE = False       # to() ignores a dtype other than float32 instead of refusing it
 
     def __init__(self):
         super().__init__()
         self._packed: Optional[_Pk] = None
-        self._epoch = 0
 
     @property
     def device(self) -> torch.device:
@@ -51,23 +53,19 @@ class F32Net(nn.Module):
         return torch.float32
 
     def to(self, *args, **kw):
-        """moves to a device; dtype=torch.float32 is accepted, any other dtype refused: the metric computes in f32 only"""
+        """moves to a device; dtype=torch.float32 is accepted, any other dtype refused (ignored under ANY_DTYPE): the network computes
+        in f32 only"""
         device, dtype = kw.get("device"), kw.get("dtype")
         for a in args:
             if isinstance(a, torch.dtype):
                 dtype = a
             elif isinstance(a, (str, torch.device, int)):
                 device = a
-        if dtype not in (None, torch.float32):
+        if dtype not in (None, torch.float32) and not self.ANY_DTYPE:
             raise ValueError(f"{type(self).__name__} computes in float32 only, got dtype={dtype}")
         if device is not None:
             super().to(device)
         return self
-
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        self._epoch += 1
-        return r
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         """every tensor of the model must be there (BatchNorm's num_batches_tracked aside) and have its shape; values are converted to
@@ -83,9 +81,7 @@ class F32Net(nn.Module):
         for k, p in own.items():
             if k in state_dict and tuple(state_dict[k].shape) != tuple(p.shape):
                 raise ValueError(f"{who}: {k!r} is {tuple(state_dict[k].shape)}, expected {tuple(p.shape)}")
-        r = super().load_state_dict({k: state_dict[k].to(own[k].dtype) if k in state_dict else own[k] for k in own}, strict=True)
-        self._epoch += 1
-        return r
+        return super().load_state_dict({k: state_dict[k].to(own[k].dtype) if k in state_dict else own[k] for k in own}, strict=True)
 
     def _fold(self, state_dict) -> _Pk:
         """state_dict -> the tree of attribute bags and lists whose tensors are the kernel layouts"""
@@ -158,6 +154,31 @@ class _HipBase:
     empty = staticmethod(lambda shape, like: torch.empty(shape, dtype=torch.float32, device=like.device))
     mean = staticmethod(ops.mean_rows_f32)
     linear = staticmethod(ops.linear_f32)
+    layernorm = staticmethod(ops.layernorm_f32)
+    attention = staticmethod(ops.attention_f32)
+    attention_causal = staticmethod(ops.attention_causal_f32)
+    gelu = staticmethod(ops.gelu_f32)
+    quick_gelu = staticmethod(ops.quick_gelu_f32)
+
+
+def run_blocks(h: torch.Tensor, blocks: Sequence[_Pk], b: int, seq: int, heads: int, eps: float, *, causal: bool = False, act: str = "gelu",
+               be=_HipBase) -> torch.Tensor:
+    """pre-LN transformer blocks on h [b * seq, C], eight launches each; `act` names the backend's activation ("gelu": erf, or
+    "quick_gelu").  A packed block is n1_g n1_b in_w in_b out_w out_b n2_g n2_b fc1_w fc1_b fc2_w fc2_b [bias_kv], in_w = q | k | v rows.
+    A block with a bias_kv pair overwrites the key / value slots of each sequence's LAST row with it (the caller left that row spare),
+    which is exactly MultiheadAttention's appended pair"""
+    c = h.shape[1]
+    attend, activate = be.attention_causal if causal else be.attention, getattr(be, act)
+    for w in blocks:
+        qkv = be.linear(be.layernorm(h, w.n1_g, w.n1_b, eps), w.in_w, w.in_b)                     # [b * seq, 3 C] = q | k | v
+        if hasattr(w, "bias_kv"):
+            slot = qkv.view(b, seq, 3 * c)[:, seq - 1, c:]
+            slot.copy_(w.bias_kv.expand_as(slot))
+        a = attend(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], b, seq, heads)
+        h = be.linear(a, w.out_w, w.out_b, res=h)
+        m = be.linear(be.layernorm(h, w.n2_g, w.n2_b, eps), w.fc1_w, w.fc1_b)
+        h = be.linear(activate(m, out=m), w.fc2_w, w.fc2_b, res=h)
+    return h
 
 
 def resolve_checkpoint(weights, env_name: str, what: str, accepted: str):

@@ -192,27 +192,9 @@ class CLIPModel(f32net.F32Net):
         return self._config[name], getattr(self.pack(device), name)
 
     # ---- forward ------------------------------------------------------------------------------------------------------------------
-    _linear = staticmethod(ops.linear_f32)
-
-    def _blocks(self, h: torch.Tensor, blocks: Sequence[_Pk], b: int, seq: int, heads: int, causal: bool = False) -> torch.Tensor:
-        """pre-LN blocks on h [b * seq, C]; a block with a bias_kv pair overwrites the key / value slots of each sequence's LAST row
-        with it (the caller left that row spare), which is exactly MultiheadAttention's appended pair"""
-        c = h.shape[1]
-        attend = ops.attention_causal_f32 if causal else ops.attention_f32
-        for w in blocks:
-            qkv = self._linear(ops.layernorm_f32(h, w.n1_g, w.n1_b, EPS), w.in_w, w.in_b)          # [b * seq, 3 C] = q | k | v
-            if hasattr(w, "bias_kv"):
-                slot = qkv.view(b, seq, 3 * c)[:, seq - 1, c:]
-                slot.copy_(w.bias_kv.expand_as(slot))
-            a = attend(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], b, seq, heads)
-            h = self._linear(a, w.out_w, w.out_b, res=h)
-            m = self._linear(ops.layernorm_f32(h, w.n2_g, w.n2_b, EPS), w.fc1_w, w.fc1_b)
-            h = self._linear(ops.gelu_f32(m, out=m), w.fc2_w, w.fc2_b, res=h)
-        return h
-
     def _head(self, rows: torch.Tensor, t: _Pk) -> torch.Tensor:
         """rows [b, C] (any row stride) -> LayerNorm, bias-free linear, L2 normalisation: (b, out) unit-norm"""
-        e = self._linear(ops.layernorm_f32(rows, t.head_g, t.head_b, EPS), t.head_w, None)
+        e = ops.linear_f32(ops.layernorm_f32(rows, t.head_g, t.head_b, EPS), t.head_w, None)
         return ops.normalize_rows_f32(e, out=e)
 
     @torch.no_grad()
@@ -227,7 +209,7 @@ class CLIPModel(f32net.F32Net):
         emb = ops.convnd_f32(x, t.stem_w, (1, p, p), (1, p, p), (0, 0, 0)).view(n * (seq - 1), -1)
         h = ops.vit_tokens_f32(emb, t.cls, t.pos, n)
         h = ops.layernorm_f32(h, t.pre_g, t.pre_b, EPS, out=h)
-        h = self._blocks(h, t.blocks, n, seq, cfg["heads"])
+        h = f32net.run_blocks(h, t.blocks, n, seq, cfg["heads"], EPS)
         return self._head(h.view(n, seq, -1)[:, 0], t)
 
     @torch.no_grad()
@@ -241,7 +223,7 @@ class CLIPModel(f32net.F32Net):
         emb = ops.convnd_f32(x, t.stem_w, (1, p, p), (1, st, st), (0, 0, 0)).view(n * (seq - 2), -1)
         emb = ops.layernorm_f32(emb, t.stem_g, t.stem_b, STEM_EPS, out=emb)
         h = ops.vit_tokens_f32(emb, t.cls, t.pos, n, tail_rows=1)
-        h = self._blocks(h, t.blocks, n, seq, cfg["heads"])
+        h = f32net.run_blocks(h, t.blocks, n, seq, cfg["heads"], EPS)
         return self._head(h.view(n, seq, -1)[:, 0], t)
 
     def tokenize(self, texts: Sequence[str]) -> torch.Tensor:
@@ -266,7 +248,7 @@ class CLIPModel(f32net.F32Net):
             raise ValueError(f"text ids must lie in [0, {cfg['vocab']})")
         n, seq = host.shape
         h = ops.embed_tokens_f32(host.to(torch.int32).contiguous().view(-1).to(dev), t.tok, t.pos, n, seq)
-        h = self._blocks(h, t.blocks, n, seq, cfg["heads"], causal=True)
+        h = f32net.run_blocks(h, t.blocks, n, seq, cfg["heads"], EPS, causal=True)
         rows = h.view(n, seq, -1)[torch.arange(n, device=dev), host.argmax(dim=-1).to(dev)]      # the first largest id: end of text
         return self._head(rows, t)
 

@@ -28,6 +28,8 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
+from .modelio import read_config
+
 
 def alphas_cumprod(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, schedule="scaled_linear") -> np.ndarray:
     if schedule == "scaled_linear":
@@ -93,13 +95,7 @@ class _Output:
 
 
 def _read_config(path: str, subfolder: Optional[str]) -> dict:
-    import json
-    import os
-
-    p = os.path.join(path, subfolder) if subfolder else path
-    with open(os.path.join(p, "scheduler_config.json")) as f:
-        cfg = json.load(f)
-    return {k: v for k, v in cfg.items() if not k.startswith("_")}
+    return read_config(path, subfolder, "scheduler_config.json", drop_private=True)
 
 
 class _ForwardProcess:

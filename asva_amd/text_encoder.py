@@ -23,11 +23,11 @@ from typing import Dict, List, Optional, Sequence, Union
 import torch
 import torch.nn as nn
 
-from . import ops
-from .weights import _Pk, pack_device
+from . import f32net, modelio, ops
+from .weights import _Pk
 
-CONFIG_NAME = "config.json"
-WEIGHT_NAMES = ("model.safetensors", "pytorch_model.bin", "diffusion_pytorch_model.safetensors", "diffusion_pytorch_model.bin")
+# transformers' names first (written as safetensors / torch.save), then diffusers'
+WEIGHT_NAMES = ("model.safetensors", "pytorch_model.bin") + modelio.WEIGHT_NAMES
 # CLIPTextConfig defaults of transformers (SD1.5's text_encoder/config.json overrides them: 768 / 3072 / 12 / 12, quick_gelu)
 DEFAULT_CONFIG = dict(vocab_size=49408, hidden_size=512, intermediate_size=2048, projection_dim=512, num_hidden_layers=12,
                       num_attention_heads=8, max_position_embeddings=77, hidden_act="quick_gelu", layer_norm_eps=1e-5,
@@ -103,25 +103,11 @@ class _TextTransformer(nn.Module):
         self.final_layer_norm = nn.LayerNorm(c, eps=cfg["layer_norm_eps"])
 
 
-def _f32_blob(tensors: List[torch.Tensor], device) -> List[torch.Tensor]:
-    """the tensors as views of ONE f32 device buffer (256-byte-aligned items): the unit a launch plan ships as a CONST region"""
-    offs, total = [], 0
-    for t in tensors:
-        offs.append(total)
-        total += (t.numel() + 63) // 64 * 64
-    blob = torch.zeros(total, dtype=torch.float32, device=device)
-    views = []
-    for t, o in zip(tensors, offs):
-        v = blob[o:o + t.numel()].view(t.shape)
-        v.copy_(t.detach().to(torch.float32))
-        views.append(v)
-    return [blob] + views
-
-
-class CLIPTextModel(nn.Module):
+class CLIPTextModel(f32net.F32Net):
     """transformers.CLIPTextModel for SD1.5's text_encoder: `model(input_ids)[0]` is the (b, 77, 768) f32 conditioning"""
 
     PREFIX = "text_model."
+    ANY_DTYPE = True        # the pipeline moves every model with .to(device, dtype=float16): the encoder computes and returns f32 regardless
 
     def __init__(self, config: Optional[Dict] = None, **kw):
         super().__init__()
@@ -132,7 +118,6 @@ class CLIPTextModel(nn.Module):
             cfg.pop(k, None)
         self._config = cfg
         self.text_model = _TextTransformer(cfg)
-        self._packed: Dict[str, _Pk] = {}
         self.requires_grad_(False)
         self.eval()
 
@@ -153,34 +138,11 @@ class CLIPTextModel(nn.Module):
     def config(self) -> _Config:
         return _Config(self._config)
 
-    @property
-    def device(self) -> torch.device:
-        return self.text_model.final_layer_norm.weight.device
-
-    @property
-    def dtype(self) -> torch.dtype:
-        return torch.float32
-
-    def to(self, *args, **kw):
-        """moves to a device; a dtype is accepted and ignored — the encoder computes and returns f32 whatever the pipeline's I/O dtype"""
-        device = kw.get("device")
-        for a in args:
-            if isinstance(a, (str, torch.device, int)):
-                device = a
-        if device is not None:
-            super().to(device)
-        return self
-
     def half(self):
         return self
 
     def float(self):
         return self
-
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        self._packed = {}
-        return r
 
     @classmethod
     def from_config(cls, config: Dict, **kw) -> "CLIPTextModel":
@@ -188,79 +150,38 @@ class CLIPTextModel(nn.Module):
 
     @classmethod
     def from_pretrained(cls, pretrained_model_path: str, subfolder: Optional[str] = "text_encoder", **_) -> "CLIPTextModel":
-        path = os.path.join(pretrained_model_path, subfolder) if subfolder else pretrained_model_path
-        with open(os.path.join(path, CONFIG_NAME)) as f:
-            model = cls(json.load(f))
-        for name in WEIGHT_NAMES:
-            file = os.path.join(path, name)
-            if os.path.isfile(file):
-                if name.endswith(".safetensors"):
-                    from safetensors.torch import load_file
-
-                    sd = load_file(file)
-                else:
-                    sd = torch.load(file, map_location="cpu", weights_only=True)
-                model.load_state_dict(sd)
-                return model
-        raise FileNotFoundError(f"none of {', '.join(WEIGHT_NAMES)} under {path}")
+        model = cls(modelio.read_config(pretrained_model_path, subfolder))
+        model.load_state_dict(modelio.read_state_dict(pretrained_model_path, subfolder, WEIGHT_NAMES))
+        return model
 
     def save_pretrained(self, save_directory: str, safe_serialization: bool = True) -> None:
-        os.makedirs(save_directory, exist_ok=True)
-        with open(os.path.join(save_directory, CONFIG_NAME), "w") as f:
-            json.dump({"architectures": ["CLIPTextModel"], "model_type": "clip_text_model", **self._config}, f, indent=2)
-        sd = {k: v.detach().cpu().contiguous() for k, v in self.state_dict().items()}
-        if safe_serialization:
-            from safetensors.torch import save_file
-
-            save_file(sd, os.path.join(save_directory, WEIGHT_NAMES[0]))
-        else:
-            torch.save(sd, os.path.join(save_directory, WEIGHT_NAMES[1]))
+        modelio.write_folder(save_directory, {"architectures": ["CLIPTextModel"], "model_type": "clip_text_model", **self._config},
+                             self.state_dict(), safe_serialization, WEIGHT_NAMES)
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         """SD1.5's names, with or without the `text_model.` prefix; `embeddings.position_ids` is ignored; a missing or an unknown
         tensor raises KeyError naming it"""
-        own = super().state_dict()
-        sd = {}
-        for k, v in state_dict.items():
-            k = k if k.startswith(self.PREFIX) else self.PREFIX + k
-            if k.endswith("embeddings.position_ids"):
-                continue
-            if k not in own:
-                raise KeyError(f"CLIPTextModel.load_state_dict: unexpected tensor {k!r}")
-            sd[k] = v.to(torch.float32)
-        for k in own:
-            if k not in sd:
-                raise KeyError(f"CLIPTextModel.load_state_dict: missing tensor {k!r}")
-        r = super().load_state_dict(sd, strict=True)
-        self._packed = {}
-        return r
+        sd = {(k if k.startswith(self.PREFIX) else self.PREFIX + k): v for k, v in state_dict.items()}
+        return super().load_state_dict({k: v for k, v in sd.items() if not k.endswith("embeddings.position_ids")}, strict=True)
 
     # ---- packing ------------------------------------------------------------------------------------------------------------------
-    def pack(self, device=None) -> _Pk:
-        """state_dict -> f32 tables and kernel-layout weights (q|k|v fused to one [3C][C] matrix) inside one device buffer; cached per
-        device, repacked after load_state_dict / .to().  Not keyed by precision.pack_key(): nothing here depends on the storage mode."""
-        device = pack_device(device)
-        if device is None and len(self._packed) == 1 and str(self.device) in self._packed:
-            return self._packed[str(self.device)]
-        device = pack_device(device, self.device, ops, "CLIPTextModel.pack")
-        pk = self._packed.get(str(device))
-        if pk is not None:
-            return pk
-        tm = self.text_model
-        flat: List[torch.Tensor] = [tm.embeddings.token_embedding.weight, tm.embeddings.position_embedding.weight,
-                                    tm.final_layer_norm.weight, tm.final_layer_norm.bias]
-        for ly in tm.encoder.layers:
-            a = ly.self_attn
-            flat += [ly.layer_norm1.weight, ly.layer_norm1.bias,
-                     torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight]), torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias]),
-                     a.out_proj.weight, a.out_proj.bias, ly.layer_norm2.weight, ly.layer_norm2.bias,
-                     ly.mlp.fc1.weight, ly.mlp.fc1.bias, ly.mlp.fc2.weight, ly.mlp.fc2.bias]
-        views = _f32_blob(flat, device)
-        names = ("ln1_g", "ln1_b", "wqkv", "bqkv", "wo", "bo", "ln2_g", "ln2_b", "w1", "b1", "w2", "b2")
-        layers = [_Pk(**dict(zip(names, views[5 + 12 * i:17 + 12 * i]))) for i in range(len(tm.encoder.layers))]
-        pk = _Pk(blob=views[0], tok=views[1], pos=views[2], lnf_g=views[3], lnf_b=views[4], layers=layers)
-        self._packed[str(device)] = pk
-        return pk
+    def _fold(self, sd) -> _Pk:
+        """f32 tables and kernel-layout weights, q | k | v fused to one [3C][C] matrix: the token table, the position table, the final
+        LayerNorm, then the layers in order.  Nothing here depends on the storage mode."""
+        def t(name):
+            return sd[self.PREFIX + name].detach().to(torch.float32)
+
+        blocks = []
+        for i in range(self._config["num_hidden_layers"]):
+            p = f"encoder.layers.{i}."
+            a = p + "self_attn."
+            blocks.append(_Pk(n1_g=t(p + "layer_norm1.weight"), n1_b=t(p + "layer_norm1.bias"),
+                              in_w=torch.cat([t(a + f"{n}_proj.weight") for n in "qkv"]), in_b=torch.cat([t(a + f"{n}_proj.bias") for n in "qkv"]),
+                              out_w=t(a + "out_proj.weight"), out_b=t(a + "out_proj.bias"),
+                              n2_g=t(p + "layer_norm2.weight"), n2_b=t(p + "layer_norm2.bias"),
+                              fc1_w=t(p + "mlp.fc1.weight"), fc1_b=t(p + "mlp.fc1.bias"), fc2_w=t(p + "mlp.fc2.weight"), fc2_b=t(p + "mlp.fc2.bias")))
+        return _Pk(tok=t("embeddings.token_embedding.weight"), pos=t("embeddings.position_embedding.weight"),
+                   lnf_g=t("final_layer_norm.weight"), lnf_b=t("final_layer_norm.bias"), blocks=blocks)
 
     # ---- forward ------------------------------------------------------------------------------------------------------------------
     def eos_positions(self, input_ids: torch.Tensor) -> torch.Tensor:
@@ -271,20 +192,12 @@ class CLIPTextModel(nn.Module):
             return ids.argmax(dim=-1)
         return (ids == self._config["eos_token_id"]).int().argmax(dim=-1)
 
-    _linear = staticmethod(ops.linear_f32)
-
     def encode_ids(self, ids: torch.Tensor, b: int, seq: int, pk: Optional[_Pk] = None) -> torch.Tensor:
         """the launches alone: ids int32 [b * seq] on the device, already checked -> [b * seq, C] after final_layer_norm"""
         pk = self.pack(ids.device) if pk is None else pk
-        heads, eps = self._config["num_attention_heads"], self._config["layer_norm_eps"]
-        c = self._config["hidden_size"]
+        eps = self._config["layer_norm_eps"]
         x = ops.embed_tokens_f32(ids, pk.tok, pk.pos, b, seq)
-        for ly in pk.layers:
-            qkv = self._linear(ops.layernorm_f32(x, ly.ln1_g, ly.ln1_b, eps), ly.wqkv, ly.bqkv)
-            a = ops.attention_causal_f32(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], b, seq, heads)
-            x = self._linear(a, ly.wo, ly.bo, res=x)
-            h = self._linear(ops.layernorm_f32(x, ly.ln2_g, ly.ln2_b, eps), ly.w1, ly.b1)
-            x = self._linear(ops.quick_gelu_f32(h, out=h), ly.w2, ly.b2, res=x)
+        x = f32net.run_blocks(x, pk.blocks, b, seq, self._config["num_attention_heads"], eps, causal=True, act="quick_gelu")
         return ops.layernorm_f32(x, pk.lnf_g, pk.lnf_b, eps)
 
     @torch.no_grad()

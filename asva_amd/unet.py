@@ -12,7 +12,6 @@ everywhere; the returned noise prediction is f32 in the reference's (B, C, F, H,
 from __future__ import annotations
 
 import inspect
-import json
 import math
 import os
 from typing import Any, Dict, Optional, Tuple, Union
@@ -23,12 +22,10 @@ from torch import nn
 from . import precision as P
 
 from . import ops
+from . import modelio
 from .conditioning import mask_to_key_index
+from .modelio import BIN_NAME, CONFIG_NAME, SAFETENSORS_NAME  # noqa: F401  (re-exported)
 from .weights import Blob, _Pk, _Ref, from_act, group_qkv, pack_conv1x1, pack_device, pack_frag, pack_geglu, pack_linear, subpixel_ups, to_act, to_planes  # noqa: F401  (_Ref: re-exported)
-
-CONFIG_NAME = "config.json"
-SAFETENSORS_NAME = "diffusion_pytorch_model.safetensors"
-BIN_NAME = "diffusion_pytorch_model.bin"
 
 DOWN_TYPES = ("FFSpatioAudioTempCrossAttnDownBlock3D", "FFSpatioTempCrossAttnDownBlock3D", "FFSpatioTempResDownBlock3D")
 UP_TYPES = ("FFSpatioAudioTempCrossAttnUpBlock3D", "FFSpatioTempCrossAttnUpBlock3D", "FFSpatioTempResUpBlock3D")
@@ -455,7 +452,7 @@ class Packer(Blob):
         return super().finish(pk, device, meta)
 
 
-class AudioUNet3DConditionModel(nn.Module):
+class AudioUNet3DConditionModel(modelio.Invalidating, nn.Module):
     config_name = CONFIG_NAME
 
     def __init__(
@@ -621,30 +618,14 @@ class AudioUNet3DConditionModel(nn.Module):
 
     @classmethod
     def load_config(cls, path: str, subfolder: Optional[str] = None) -> Dict[str, Any]:
-        if subfolder:
-            path = os.path.join(path, subfolder)
-        with open(os.path.join(path, CONFIG_NAME)) as f:
-            return json.load(f)
-
-    @staticmethod
-    def _read_weights(path: str) -> Dict[str, torch.Tensor]:
-        st = os.path.join(path, SAFETENSORS_NAME)
-        if os.path.isfile(st):
-            from safetensors.torch import load_file
-
-            return load_file(st)
-        bn = os.path.join(path, BIN_NAME)
-        if os.path.isfile(bn):
-            return torch.load(bn, map_location="cpu", weights_only=True)
-        raise FileNotFoundError(f"no {SAFETENSORS_NAME} or {BIN_NAME} under {path}")
+        return modelio.read_config(path, subfolder)
 
     @classmethod
     def from_pretrained(cls, pretrained_model_path: str, subfolder: Optional[str] = None, torch_dtype=None, **_):
         """Reads the diffusers directory layout the reference trainer writes
         (audio_cond_animation_trainer.py:152-155; loaded at pipeline_audio_cond_animation.py:516)."""
-        path = os.path.join(pretrained_model_path, subfolder) if subfolder else pretrained_model_path
-        model = cls.from_config(cls.load_config(path))
-        model.load_state_dict(cls._read_weights(path))
+        model = cls.from_config(cls.load_config(pretrained_model_path, subfolder))
+        model.load_state_dict(modelio.read_state_dict(pretrained_model_path, subfolder))
         if torch_dtype is not None:
             model = model.to(torch_dtype)
         return model.eval()
@@ -653,8 +634,7 @@ class AudioUNet3DConditionModel(nn.Module):
     def from_pretrained_2d(cls, config3d, pretrained_model_path: str, subfolder: Optional[str] = None):
         """2-D -> 3-D inflation (audio_cond_unet_3d_condition.py:800-838): every key containing
         '_temp', every key missing from the 2-D checkpoint and every shape mismatch keeps the fresh init."""
-        path = os.path.join(pretrained_model_path, subfolder) if subfolder else pretrained_model_path
-        cfg = cls.load_config(path)
+        cfg = cls.load_config(pretrained_model_path, subfolder)
         cfg["_class_name"] = cls.__name__
         cfg["down_block_types"] = tuple(config3d["down_block_types"])
         cfg["up_block_types"] = tuple(config3d["up_block_types"])
@@ -663,7 +643,7 @@ class AudioUNet3DConditionModel(nn.Module):
             if k in config3d:
                 cfg[k] = config3d[k]
         model = cls.from_config(cfg)
-        sd2d = cls._read_weights(path)
+        sd2d = modelio.read_state_dict(pretrained_model_path, subfolder)
         for k, v in model.state_dict().items():
             if "_temp" in k or k not in sd2d or sd2d[k].shape != v.shape:
                 sd2d[k] = v
@@ -671,28 +651,7 @@ class AudioUNet3DConditionModel(nn.Module):
         return model
 
     def save_pretrained(self, save_directory: str, safe_serialization: bool = True):
-        os.makedirs(save_directory, exist_ok=True)
-        cfg = {"_class_name": type(self).__name__, "_diffusers_version": "0.29.2"}
-        cfg.update({k: (list(v) if isinstance(v, tuple) else v) for k, v in self.config.items()})
-        with open(os.path.join(save_directory, CONFIG_NAME), "w") as f:
-            json.dump(cfg, f, indent=2)
-        sd = {k: v.detach().cpu().contiguous() for k, v in self.state_dict().items()}
-        if safe_serialization:
-            from safetensors.torch import save_file
-
-            save_file(sd, os.path.join(save_directory, SAFETENSORS_NAME))
-        else:
-            torch.save(sd, os.path.join(save_directory, BIN_NAME))
-
-    def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        r = super().load_state_dict(state_dict, strict=strict, **kw)
-        self._invalidate()
-        return r
-
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        self._invalidate()
-        return r
+        modelio.write_folder(save_directory, modelio.diffusers_config(self, self.config), self.state_dict(), safe_serialization)
 
     def _invalidate(self):
         self._packed = None

@@ -14,8 +14,6 @@ LDS-direct GEMM tiles.
 """
 from __future__ import annotations
 
-import json
-import os
 from typing import Optional
 
 import torch
@@ -23,7 +21,7 @@ import torch
 from . import precision as P
 from torch import nn
 
-from . import ops
+from . import modelio, ops
 from .unet import FrozenConfig, _Affine, _Conv, _Linear
 from .weights import Blob, _Pk, pack_conv1x1, pack_conv3x3, pack_device, pack_linear, subpixel_ups, to_act
 
@@ -151,7 +149,7 @@ class _Decoder(nn.Module):
 _LEGACY_ATTN = {"query": "to_q", "key": "to_k", "value": "to_v", "proj_attn": "to_out.0"}
 
 
-class AutoencoderKL(nn.Module):
+class AutoencoderKL(modelio.Invalidating, nn.Module):
     def __init__(self, in_channels=3, out_channels=3, down_block_types=("DownEncoderBlock2D",) * 4,
                  up_block_types=("UpDecoderBlock2D",) * 4, block_out_channels=(128, 256, 512, 512), layers_per_block=2,
                  act_fn="silu", latent_channels=4, norm_num_groups=32, sample_size=512, scaling_factor=0.18215,
@@ -190,33 +188,13 @@ class AutoencoderKL(nn.Module):
 
     @classmethod
     def from_pretrained(cls, path: str, subfolder: Optional[str] = None, **_):
-        p = os.path.join(path, subfolder) if subfolder else path
-        with open(os.path.join(p, "config.json")) as f:
-            model = cls.from_config(json.load(f))
-        st = os.path.join(p, "diffusion_pytorch_model.safetensors")
-        if os.path.isfile(st):
-            from safetensors.torch import load_file
-
-            sd = load_file(st)
-        else:
-            sd = torch.load(os.path.join(p, "diffusion_pytorch_model.bin"), map_location="cpu", weights_only=True)
-        model.load_state_dict(sd)
+        model = cls.from_config(modelio.read_config(path, subfolder))
+        model.load_state_dict(modelio.read_state_dict(path, subfolder))
         return model.eval()
 
     def save_pretrained(self, save_directory: str, safe_serialization: bool = True):
         """diffusers directory layout: config.json + diffusion_pytorch_model.safetensors (current attention names)."""
-        os.makedirs(save_directory, exist_ok=True)
-        cfg = {"_class_name": "AutoencoderKL", "_diffusers_version": "0.29.2"}
-        cfg.update({k: (list(v) if isinstance(v, tuple) else v) for k, v in dict(self.config).items()})
-        with open(os.path.join(save_directory, "config.json"), "w") as f:
-            json.dump(cfg, f, indent=2)
-        sd = {k: v.detach().cpu().contiguous() for k, v in self.state_dict().items()}
-        if safe_serialization:
-            from safetensors.torch import save_file
-
-            save_file(sd, os.path.join(save_directory, "diffusion_pytorch_model.safetensors"))
-        else:
-            torch.save(sd, os.path.join(save_directory, "diffusion_pytorch_model.bin"))
+        modelio.write_folder(save_directory, modelio.diffusers_config(self, self.config), self.state_dict(), safe_serialization)
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         """Accepts diffusers AutoencoderKL checkpoints of either vintage: legacy attention names
@@ -231,14 +209,10 @@ class AutoencoderKL(nn.Module):
                 if k.endswith("weight") and v.dim() == 4 and "group_norm" not in k:
                     v = v.reshape(v.shape[0], v.shape[1])
             sd[k] = v
-        r = super().load_state_dict(sd, strict=strict, **kw)
-        self._packed = None
-        return r
+        return super().load_state_dict(sd, strict=strict, **kw)
 
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
+    def _invalidate(self) -> None:
         self._packed = None
-        return r
 
     @torch.no_grad()
     def encode(self, x: torch.Tensor, return_dict: bool = True):
