@@ -106,117 +106,115 @@ __global__ __launch_bounds__(256) void linear_small_m_kernel(const float* x, con
   }
 }
 
-struct GuidedArgs {
-  const float* noise_pred; float* eps_hist; const float* x_in; float* x_out;
+// What the three scheduler-step kernels share: the CFG batch, the history ring and the latents (include/avsd.h)
+struct StepArgs {
+  const float* noise_pred; float* hist; const float* x_in; float* x_out;
   int n_branch, store_slot, n_hist;
   int hist_idx[4];
-  float w[4];
-  float g, g2, w_cur, ca, cb;
+  float g, g2;
   int B, C, F, HW;
 };
 
+// guided epsilon of element i: e0 + g (e1 - e0) [+ g2 (e2 - e1)], audio-only / text-only guidance, or the dual form of
+// pipeline_audio_cond_animation.py:349-353 with branches [uncond, text, text+audio], g = text scale, g2 = audio scale
+__device__ __forceinline__ float guided_eps(const StepArgs& s, int64_t per, int64_t i) {
+  float eps = s.noise_pred[i];
+  if (s.n_branch >= 2) {
+    const float e1 = s.noise_pred[per + i];
+    float gsum = eps + s.g * (e1 - eps);
+    if (s.n_branch == 3) gsum = gsum + s.g2 * (s.noise_pred[2 * per + i] - e1);
+    eps = gsum;
+  }
+  return eps;
+}
+
+// element i lies in frame 0, the pinned image latent that no step updates
+__device__ __forceinline__ bool first_frame(const StepArgs& s, int64_t i) {
+  return (i % ((int64_t)s.F * s.HW)) / s.HW == 0;
+}
+
+struct GuidedArgs {
+  StepArgs s;
+  float w[4];
+  float w_cur, ca, cb;
+};
+
 __global__ void guided_step_kernel(const GuidedArgs a) {
-  const int64_t per = (int64_t)a.B * a.C * a.F * a.HW;   // elements of one latent tensor
-  const int64_t fhw = (int64_t)a.F * a.HW;
+  const StepArgs& s = a.s;
+  const int64_t per = (int64_t)s.B * s.C * s.F * s.HW;   // elements of one latent tensor
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < per; i += (int64_t)gridDim.x * blockDim.x) {
-    float eps = a.noise_pred[i];
-    if (a.n_branch >= 2) {
-      // e0 + g (e1 - e0) [+ g2 (e2 - e1)]: audio-only / text-only guidance, or the dual form of
-      // pipeline_audio_cond_animation.py:349-353 with branches [uncond, text, text+audio], g = text scale, g2 = audio scale
-      const float e1 = a.noise_pred[per + i];
-      float gsum = eps + a.g * (e1 - eps);
-      if (a.n_branch == 3) gsum = gsum + a.g2 * (a.noise_pred[2 * per + i] - e1);
-      eps = gsum;
-    }
-    if (a.eps_hist && a.store_slot >= 0) a.eps_hist[(int64_t)a.store_slot * per + i] = eps;
+    const float eps = guided_eps(s, per, i);
+    if (s.hist && s.store_slot >= 0) s.hist[(int64_t)s.store_slot * per + i] = eps;
     float e = a.w_cur * eps;
-    for (int k = 0; k < a.n_hist; ++k) {
+    for (int k = 0; k < s.n_hist; ++k) {
       // the freshly stored slot is read back from the register copy
-      const float h = (a.hist_idx[k] == a.store_slot) ? eps : a.eps_hist[(int64_t)a.hist_idx[k] * per + i];
+      const float h = (s.hist_idx[k] == s.store_slot) ? eps : s.hist[(int64_t)s.hist_idx[k] * per + i];
       e = fmaf(a.w[k], h, e);
     }
-    const int f = (int)((i % fhw) / a.HW);
-    const float xin = a.x_in[i];
-    a.x_out[i] = (f == 0) ? xin : fmaf(a.ca, xin, a.cb * e);
+    const float xin = s.x_in[i];
+    s.x_out[i] = first_frame(s, i) ? xin : fmaf(a.ca, xin, a.cb * e);
   }
 }
 
 struct MultistepArgs {
-  const float* noise_pred; float* hist; const float* x_in; float* x_out;
-  int n_branch, store_slot, n_hist;
-  int hist_idx[4];
+  StepArgs s;
   float w[4];
-  float g, g2, ca, c_cur, s_x, s_e;
-  int B, C, F, HW;
+  float ca, c_cur, s_x, s_e;
 };
 
 // DPM-Solver++ step: the ring holds data predictions d = s_x x + s_e eps of earlier steps (include/avsd.h)
 __global__ void guided_multistep_kernel(const MultistepArgs a) {
-  const int64_t per = (int64_t)a.B * a.C * a.F * a.HW;
-  const int64_t fhw = (int64_t)a.F * a.HW;
+  const StepArgs& s = a.s;
+  const int64_t per = (int64_t)s.B * s.C * s.F * s.HW;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < per; i += (int64_t)gridDim.x * blockDim.x) {
-    float eps = a.noise_pred[i];
-    if (a.n_branch >= 2) {      // the guidance rule of guided_step_kernel
-      const float e1 = a.noise_pred[per + i];
-      float gsum = eps + a.g * (e1 - eps);
-      if (a.n_branch == 3) gsum = gsum + a.g2 * (a.noise_pred[2 * per + i] - e1);
-      eps = gsum;
-    }
-    const float xin = a.x_in[i];
+    const float eps = guided_eps(s, per, i);
+    const float xin = s.x_in[i];
     const float d = fmaf(a.s_x, xin, a.s_e * eps);
-    if (a.hist && a.store_slot >= 0) a.hist[(int64_t)a.store_slot * per + i] = d;
+    if (s.hist && s.store_slot >= 0) s.hist[(int64_t)s.store_slot * per + i] = d;
     float acc = fmaf(a.c_cur, d, a.ca * xin);
-    for (int k = 0; k < a.n_hist; ++k) {
-      const float h = (a.hist_idx[k] == a.store_slot) ? d : a.hist[(int64_t)a.hist_idx[k] * per + i];
+    for (int k = 0; k < s.n_hist; ++k) {
+      const float h = (s.hist_idx[k] == s.store_slot) ? d : s.hist[(int64_t)s.hist_idx[k] * per + i];
       acc = fmaf(a.w[k], h, acc);
     }
-    const int f = (int)((i % fhw) / a.HW);
-    a.x_out[i] = (f == 0) ? xin : acc;
+    s.x_out[i] = first_frame(s, i) ? xin : acc;
   }
 }
 
 struct UniPCArgs {
-  const float* noise_pred; float* hist; const float* x_in; float* x_out; float* x_last;
-  int n_branch, store_slot, n_hist, use_corrector;
-  int hist_idx[4];
+  StepArgs s;
+  float* x_last;
+  int use_corrector;
   float wc[4], wp[4];
-  float g, g2, s_x, s_e, cc_last, cc_cur, cp_x, cp_cur;
-  int B, C, F, HW;
+  float s_x, s_e, cc_last, cc_cur, cp_x, cp_cur;
 };
 
 // UniPC step: the corrector of the sample the UNet just saw, then the predictor for the next sigma (include/avsd.h).  Unlike the
 // two kernels above, every history slot is read BEFORE this step's data prediction is stored, so the store may take the oldest one.
 __global__ void guided_unipc_kernel(const UniPCArgs a) {
-  const int64_t per = (int64_t)a.B * a.C * a.F * a.HW;
-  const int64_t fhw = (int64_t)a.F * a.HW;
+  const StepArgs& s = a.s;
+  const int64_t per = (int64_t)s.B * s.C * s.F * s.HW;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < per; i += (int64_t)gridDim.x * blockDim.x) {
-    float eps = a.noise_pred[i];
-    if (a.n_branch >= 2) {      // the guidance rule of guided_step_kernel
-      const float e1 = a.noise_pred[per + i];
-      float gsum = eps + a.g * (e1 - eps);
-      if (a.n_branch == 3) gsum = gsum + a.g2 * (a.noise_pred[2 * per + i] - e1);
-      eps = gsum;
-    }
-    const float xin = a.x_in[i];
+    const float eps = guided_eps(s, per, i);
+    const float xin = s.x_in[i];
     const float d = fmaf(a.s_x, xin, a.s_e * eps);
     float h[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) h[k] = (k < a.n_hist) ? a.hist[(int64_t)a.hist_idx[k] * per + i] : 0.f;
+    for (int k = 0; k < 4; ++k) h[k] = (k < s.n_hist) ? s.hist[(int64_t)s.hist_idx[k] * per + i] : 0.f;
     float xc = xin;
     if (a.use_corrector) {
       xc = fmaf(a.cc_cur, d, a.cc_last * a.x_last[i]);
 #pragma unroll
       for (int k = 0; k < 4; ++k)
-        if (k < a.n_hist) xc = fmaf(a.wc[k], h[k], xc);
+        if (k < s.n_hist) xc = fmaf(a.wc[k], h[k], xc);
     }
     float acc = fmaf(a.cp_cur, d, a.cp_x * xc);
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      if (k < a.n_hist) acc = fmaf(a.wp[k], h[k], acc);
-    const bool first = (i % fhw) / a.HW == 0;
-    if (a.store_slot >= 0) a.hist[(int64_t)a.store_slot * per + i] = d;
+      if (k < s.n_hist) acc = fmaf(a.wp[k], h[k], acc);
+    const bool first = first_frame(s, i);
+    if (s.store_slot >= 0) s.hist[(int64_t)s.store_slot * per + i] = d;
     a.x_last[i] = first ? xin : xc;
-    a.x_out[i] = first ? xin : acc;
+    s.x_out[i] = first ? xin : acc;
   }
 }
 
@@ -328,6 +326,25 @@ __global__ void xattn_pack_kv_kernel(const h16_t* kv, int rows, int C, const int
   }
 }
 
+// The checks of the three avsd_guided_* entry points on what they share, then `s` filled in with the ring table padded to 4
+// entries; `who` prefixes the messages, `tables`: every weight table of the entry point is there.
+int step_require(const char* who, StepArgs& s, const float* noise_pred, int n_branch, float g, float g2, float* hist, int store_slot,
+                 const int32_t* hist_idx, bool tables, int n_hist, const float* x_in, float* x_out, int B, int C, int F, int HW) {
+  AVSD_REQUIRE(noise_pred && x_in && x_out, "%s: null pointer", who);
+  AVSD_REQUIRE(n_branch >= 1 && n_branch <= 3, "%s: n_branch must be 1, 2 or 3", who);
+  AVSD_REQUIRE(n_hist >= 0 && n_hist <= 4, "%s: n_hist must be in [0, 4]", who);
+  AVSD_REQUIRE((n_hist == 0 && store_slot < 0) || hist, "%s: history requested without hist", who);
+  AVSD_REQUIRE(n_hist == 0 || (hist_idx && tables), "%s: null history tables", who);
+  AVSD_REQUIRE(B > 0 && C > 0 && F > 0 && HW > 0, "%s: bad shape", who);
+  s = StepArgs{noise_pred, hist, x_in, x_out, n_branch, store_slot, n_hist, {0, 0, 0, 0}, g, g2, B, C, F, HW};
+  for (int k = 0; k < n_hist; ++k) s.hist_idx[k] = hist_idx[k];
+  return AVSD_OK;
+}
+
+inline void pad4(float* dst, const float* src, int n) {
+  for (int k = 0; k < 4; ++k) dst[k] = k < n ? src[k] : 0.f;
+}
+
 }  // namespace
 
 extern "C" int avsd_ncfhw_to_rows_x2(const float* src, void* dst, int64_t dst_lo, int B, int C, int F, int HW, int cpad, int rep,
@@ -394,18 +411,12 @@ extern "C" int avsd_linear_small_m(const float* x, const void* W, const float* b
 extern "C" int avsd_guided_step(const float* noise_pred, int n_branch, float g, float g2, float* eps_hist, int store_slot,
                                 float w_cur, const int32_t* hist_idx, const float* w, int n_hist, const float* x_in,
                                 float* x_out, float ca, float cb, int B, int C, int F, int HW, void* stream) {
-  AVSD_REQUIRE(noise_pred && x_in && x_out, "guided_step: null pointer");
-  AVSD_REQUIRE(n_branch >= 1 && n_branch <= 3, "guided_step: n_branch must be 1, 2 or 3");
-  AVSD_REQUIRE(n_hist >= 0 && n_hist <= 4, "guided_step: n_hist must be in [0, 4]");
-  AVSD_REQUIRE((n_hist == 0 && store_slot < 0) || eps_hist, "guided_step: history requested without eps_hist");
-  AVSD_REQUIRE(n_hist == 0 || (hist_idx && w), "guided_step: null history tables");
-  AVSD_REQUIRE(B > 0 && C > 0 && F > 0 && HW > 0, "guided_step: bad shape");
   GuidedArgs a;
-  a.noise_pred = noise_pred; a.eps_hist = eps_hist; a.x_in = x_in; a.x_out = x_out;
-  a.n_branch = n_branch; a.store_slot = store_slot; a.n_hist = n_hist;
-  for (int k = 0; k < 4; ++k) { a.hist_idx[k] = k < n_hist ? hist_idx[k] : 0; a.w[k] = k < n_hist ? w[k] : 0.f; }
-  a.g = g; a.g2 = g2; a.w_cur = w_cur; a.ca = ca; a.cb = cb;
-  a.B = B; a.C = C; a.F = F; a.HW = HW;
+  if (int rc = step_require("guided_step", a.s, noise_pred, n_branch, g, g2, eps_hist, store_slot, hist_idx, w != nullptr, n_hist, x_in,
+                            x_out, B, C, F, HW))
+    return rc;
+  pad4(a.w, w, n_hist);
+  a.w_cur = w_cur; a.ca = ca; a.cb = cb;
   const int64_t n = (int64_t)B * C * F * HW;
   hipLaunchKernelGGL(guided_step_kernel, dim3(grid_for(n, 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
   AVSD_CHECK_LAUNCH("guided_step launch");
@@ -415,18 +426,12 @@ extern "C" int avsd_guided_step(const float* noise_pred, int n_branch, float g, 
 extern "C" int avsd_guided_multistep(const float* noise_pred, int n_branch, float g, float g2, float* hist, int store_slot,
                                      const int32_t* hist_idx, const float* w, int n_hist, const float* x_in, float* x_out,
                                      float ca, float c_cur, float s_x, float s_e, int B, int C, int F, int HW, void* stream) {
-  AVSD_REQUIRE(noise_pred && x_in && x_out, "guided_multistep: null pointer");
-  AVSD_REQUIRE(n_branch >= 1 && n_branch <= 3, "guided_multistep: n_branch must be 1, 2 or 3");
-  AVSD_REQUIRE(n_hist >= 0 && n_hist <= 4, "guided_multistep: n_hist must be in [0, 4]");
-  AVSD_REQUIRE((n_hist == 0 && store_slot < 0) || hist, "guided_multistep: history requested without hist");
-  AVSD_REQUIRE(n_hist == 0 || (hist_idx && w), "guided_multistep: null history tables");
-  AVSD_REQUIRE(B > 0 && C > 0 && F > 0 && HW > 0, "guided_multistep: bad shape");
   MultistepArgs a;
-  a.noise_pred = noise_pred; a.hist = hist; a.x_in = x_in; a.x_out = x_out;
-  a.n_branch = n_branch; a.store_slot = store_slot; a.n_hist = n_hist;
-  for (int k = 0; k < 4; ++k) { a.hist_idx[k] = k < n_hist ? hist_idx[k] : 0; a.w[k] = k < n_hist ? w[k] : 0.f; }
-  a.g = g; a.g2 = g2; a.ca = ca; a.c_cur = c_cur; a.s_x = s_x; a.s_e = s_e;
-  a.B = B; a.C = C; a.F = F; a.HW = HW;
+  if (int rc = step_require("guided_multistep", a.s, noise_pred, n_branch, g, g2, hist, store_slot, hist_idx, w != nullptr, n_hist, x_in,
+                            x_out, B, C, F, HW))
+    return rc;
+  pad4(a.w, w, n_hist);
+  a.ca = ca; a.c_cur = c_cur; a.s_x = s_x; a.s_e = s_e;
   const int64_t n = (int64_t)B * C * F * HW;
   hipLaunchKernelGGL(guided_multistep_kernel, dim3(grid_for(n, 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
   AVSD_CHECK_LAUNCH("guided_multistep launch");
@@ -437,24 +442,17 @@ extern "C" int avsd_guided_unipc(const float* noise_pred, int n_branch, float g,
                                  const int32_t* hist_idx, const float* wc, const float* wp, int n_hist, const float* x_in,
                                  float* x_out, float* x_last, int use_corrector, float s_x, float s_e, float cc_last,
                                  float cc_cur, float cp_x, float cp_cur, int B, int C, int F, int HW, void* stream) {
-  AVSD_REQUIRE(noise_pred && x_in && x_out && x_last, "guided_unipc: null pointer");
-  AVSD_REQUIRE(n_branch >= 1 && n_branch <= 3, "guided_unipc: n_branch must be 1, 2 or 3");
-  AVSD_REQUIRE(n_hist >= 0 && n_hist <= 4, "guided_unipc: n_hist must be in [0, 4]");
-  AVSD_REQUIRE((n_hist == 0 && store_slot < 0) || hist, "guided_unipc: history requested without hist");
-  AVSD_REQUIRE(n_hist == 0 || (hist_idx && wc && wp), "guided_unipc: null history tables");
-  AVSD_REQUIRE(x_last != x_in && x_last != x_out, "guided_unipc: x_last must not alias x_in or x_out");
-  AVSD_REQUIRE(B > 0 && C > 0 && F > 0 && HW > 0, "guided_unipc: bad shape");
-  for (int k = 0; k < n_hist; ++k) AVSD_REQUIRE(hist_idx[k] >= 0, "guided_unipc: negative history slot");
+  AVSD_REQUIRE(x_last, "guided_unipc: null pointer");
   UniPCArgs a;
-  a.noise_pred = noise_pred; a.hist = hist; a.x_in = x_in; a.x_out = x_out; a.x_last = x_last;
-  a.n_branch = n_branch; a.store_slot = store_slot; a.n_hist = n_hist; a.use_corrector = use_corrector != 0;
-  for (int k = 0; k < 4; ++k) {
-    a.hist_idx[k] = k < n_hist ? hist_idx[k] : 0;
-    a.wc[k] = k < n_hist ? wc[k] : 0.f;
-    a.wp[k] = k < n_hist ? wp[k] : 0.f;
-  }
-  a.g = g; a.g2 = g2; a.s_x = s_x; a.s_e = s_e; a.cc_last = cc_last; a.cc_cur = cc_cur; a.cp_x = cp_x; a.cp_cur = cp_cur;
-  a.B = B; a.C = C; a.F = F; a.HW = HW;
+  if (int rc = step_require("guided_unipc", a.s, noise_pred, n_branch, g, g2, hist, store_slot, hist_idx, wc && wp, n_hist, x_in, x_out,
+                            B, C, F, HW))
+    return rc;
+  AVSD_REQUIRE(x_last != x_in && x_last != x_out, "guided_unipc: x_last must not alias x_in or x_out");
+  for (int k = 0; k < n_hist; ++k) AVSD_REQUIRE(hist_idx[k] >= 0, "guided_unipc: negative history slot");
+  a.x_last = x_last; a.use_corrector = use_corrector != 0;
+  pad4(a.wc, wc, n_hist);
+  pad4(a.wp, wp, n_hist);
+  a.s_x = s_x; a.s_e = s_e; a.cc_last = cc_last; a.cc_cur = cc_cur; a.cp_x = cp_x; a.cp_cur = cp_cur;
   const int64_t n = (int64_t)B * C * F * HW;
   hipLaunchKernelGGL(guided_unipc_kernel, dim3(grid_for(n, 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
   AVSD_CHECK_LAUNCH("guided_unipc launch");

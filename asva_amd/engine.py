@@ -15,7 +15,6 @@ from typing import Optional
 import torch
 
 from . import ops
-from .schedulers import MultistepPlan, UniPCPlan
 
 
 class DenoiseEngine:
@@ -111,22 +110,9 @@ class DenoiseEngine:
 
     def step(self, latents: torch.Tensor, i: int) -> None:
         """One denoising step in place on `latents` (b, 4, F, H, W) f32: UNet on the CFG batch, then the guidance mix
-        (see __init__), scheduler update of frames 1.., frame 0 untouched."""
-        p = self._plans[i]
+        (see __init__), scheduler update of frames 1.., frame 0 untouched: the step's plan launches its own kernel (schedulers.py)."""
         noise = self.unet_step(latents, self._ts[i:i + 1])
-        if isinstance(p, MultistepPlan):        # DPM-Solver++: the ring holds data predictions
-            ops.guided_multistep(noise, self.n_branch, self.g, latents, latents, p.ca, p.c_cur, p.s_x, p.s_e, hist=self._hist,
-                                 store_slot=p.store_slot, hist_idx=p.hist_idx, w=p.hist_w, g2=self.g2)
-            return
-        if isinstance(p, UniPCPlan):            # UniPC: corrector of the sample the UNet saw, then predictor, one launch
-            ops.guided_unipc(noise, self.n_branch, self.g, latents, latents, self._x_last, p.use_corrector, p.s_x, p.s_e, p.cc_last,
-                             p.cc_cur, p.cp_x, p.cp_cur, hist=self._hist, store_slot=p.store_slot, hist_idx=p.hist_idx, wc=p.wc,
-                             wp=p.wp, g2=self.g2)
-            return
-        if p.save_sample:                       # StepPlan: PNDM / DDIM
-            ops.copy(latents, self._saved)
-        ops.guided_step(noise, self.n_branch, self.g, self._saved if p.use_saved_sample else latents, latents, p.ca, p.cb,
-                        eps_hist=self._hist, store_slot=p.store_slot, w_cur=p.w_cur, hist_idx=p.hist_idx, w=p.hist_w, g2=self.g2)
+        self._plans[i].launch(ops, noise, self.n_branch, self.g, self.g2, latents, self)
 
     @torch.no_grad()
     def run(self, latents: torch.Tensor, num_inference_steps: int) -> torch.Tensor:

@@ -1365,18 +1365,38 @@ def timestep_embedding(t: torch.Tensor, dim: int) -> torch.Tensor:
     return out
 
 
+def _step_args(who: str, noise_pred, n_branch: int, xs, hist, store_slot: int, hist_idx, **weights):
+    """What the three fused scheduler steps check and build alike.  `xs` = (x_in, x_out[, x_last]): contiguous f32 device tensors of
+    one 5-d shape, noise_pred n_branch times that size; `hist` (slots, *x_in.shape) holds every ring slot named; one weight per
+    hist_idx entry in each table.  -> (B, C, F, H * W), n_hist, the hist_idx table and the weight tables, padded to 4 entries"""
+    names = ("x_in", "x_out", "x_last")[:len(xs)]
+    for t, name in zip((noise_pred, *xs), ("noise_pred", *names)):
+        _req(t, F32, name)
+    x_in = xs[0]
+    if (x_in.dim() != 5 or not all(t.is_contiguous() and t.shape == x_in.shape for t in xs) or not noise_pred.is_contiguous()
+            or noise_pred.numel() != n_branch * x_in.numel()):
+        raise ValueError(f"{who}: contiguous {' / '.join(names)} of one shape (B, C, F, H, W) and noise_pred of n_branch times their size")
+    nh = len(hist_idx)
+    if nh > 4 or any(len(w) != nh for w in weights.values()):
+        raise ValueError(f"{who}: at most 4 history entries, with one {' and one '.join(weights)} weight each")
+    slots = [s for s in (store_slot, *hist_idx) if s >= 0]
+    if min(hist_idx, default=0) < 0 or (slots and (
+            hist is None or not hist.is_contiguous() or hist.dtype != F32 or hist.device != x_in.device
+            or tuple(hist.shape[1:]) != tuple(x_in.shape) or max(slots) >= hist.shape[0])):
+        raise ValueError(f"{who}: slots {store_slot} / {tuple(hist_idx)} need hist_idx >= 0 and a contiguous f32 hist of shape "
+                         f"(> {max(slots, default=0)}, {tuple(x_in.shape)}) on the latents' device")
+    B, Cc, Fr, H, W = x_in.shape
+    return ((B, Cc, Fr, H * W), nh, (C.c_int32 * 4)(*hist_idx, *[0] * (4 - nh)),
+            [(C.c_float * 4)(*w, *[0.0] * (4 - nh)) for w in weights.values()])
+
+
 def guided_step(noise_pred: torch.Tensor, n_branch: int, g: float, x_in: torch.Tensor, x_out: torch.Tensor,
                 ca: float, cb: float, *, eps_hist: Optional[torch.Tensor] = None, store_slot: int = -1,
                 w_cur: float = 1.0, hist_idx=(), w=(), g2: float = 0.0) -> None:
-    _req(noise_pred, F32, "noise_pred")
-    _req(x_in, F32, "x_in")
-    _req(x_out, F32, "x_out")
-    B, Cc, Fr, H, W = x_in.shape
-    nh = len(hist_idx)
-    idx = (C.c_int32 * 4)(*(list(hist_idx) + [0] * (4 - nh)))
-    ws = (C.c_float * 4)(*(list(w) + [0.0] * (4 - nh)))
+    """avsd_guided_step (include/avsd.h): one PLMS / DDIM step in place or out of place; `eps_hist` is (slots, *x_in.shape)."""
+    (B, Cc, Fr, HW), nh, idx, (ws,) = _step_args("guided_step", noise_pred, n_branch, (x_in, x_out), eps_hist, store_slot, hist_idx, w=w)
     check(_lib.lib().avsd_guided_step(_p(noise_pred), n_branch, float(g), float(g2), _p(eps_hist), store_slot, float(w_cur), idx, ws,
-                                      nh, _p(x_in), _p(x_out), float(ca), float(cb), B, Cc, Fr, H * W, _stream()),
+                                      nh, _p(x_in), _p(x_out), float(ca), float(cb), B, Cc, Fr, HW, _stream()),
           "avsd_guided_step")
 
 
@@ -1384,22 +1404,9 @@ def guided_multistep(noise_pred: torch.Tensor, n_branch: int, g: float, x_in: to
                      ca: float, c_cur: float, s_x: float, s_e: float, *, hist: Optional[torch.Tensor] = None, store_slot: int = -1,
                      hist_idx=(), w=(), g2: float = 0.0) -> None:
     """avsd_guided_multistep (include/avsd.h): one DPM-Solver++ step in place or out of place; `hist` is (slots, *x_in.shape)."""
-    _req(noise_pred, F32, "noise_pred")
-    _req(x_in, F32, "x_in")
-    _req(x_out, F32, "x_out")
-    B, Cc, Fr, H, W = x_in.shape
-    if not (x_in.is_contiguous() and x_out.is_contiguous() and x_out.shape == x_in.shape and noise_pred.is_contiguous()
-            and noise_pred.numel() == n_branch * x_in.numel()):
-        raise ValueError("guided_multistep: contiguous x_in / x_out of one shape and noise_pred of n_branch times their size")
-    slots = [s for s in (store_slot, *hist_idx) if s >= 0]
-    if slots and (hist is None or not hist.is_contiguous() or hist.dtype != F32 or tuple(hist.shape[1:]) != tuple(x_in.shape)
-                  or max(slots) >= hist.shape[0] or min(hist_idx, default=0) < 0):
-        raise ValueError(f"guided_multistep: slots {slots} need a contiguous f32 hist of shape (> {max(slots)}, {tuple(x_in.shape)})")
-    nh = len(hist_idx)
-    idx = (C.c_int32 * 4)(*(list(hist_idx) + [0] * (4 - nh)))
-    ws = (C.c_float * 4)(*(list(w) + [0.0] * (4 - nh)))
+    (B, Cc, Fr, HW), nh, idx, (ws,) = _step_args("guided_multistep", noise_pred, n_branch, (x_in, x_out), hist, store_slot, hist_idx, w=w)
     check(_lib.lib().avsd_guided_multistep(_p(noise_pred), n_branch, float(g), float(g2), _p(hist), store_slot, idx, ws, nh,
-                                           _p(x_in), _p(x_out), float(ca), float(c_cur), float(s_x), float(s_e), B, Cc, Fr, H * W,
+                                           _p(x_in), _p(x_out), float(ca), float(c_cur), float(s_x), float(s_e), B, Cc, Fr, HW,
                                            _stream()),
           "avsd_guided_multistep")
 
@@ -1409,30 +1416,14 @@ def guided_unipc(noise_pred: torch.Tensor, n_branch: int, g: float, x_in: torch.
                  hist: Optional[torch.Tensor] = None, store_slot: int = -1, hist_idx=(), wc=(), wp=(), g2: float = 0.0) -> None:
     """avsd_guided_unipc (include/avsd.h): one UniPC step (corrector of x_in from x_last, then predictor), x_out in place or out of
     place; `x_last` receives the corrected sample and aliases neither; `hist` is (slots, *x_in.shape)."""
-    _req(noise_pred, F32, "noise_pred")
-    _req(x_in, F32, "x_in")
-    _req(x_out, F32, "x_out")
-    _req(x_last, F32, "x_last")
-    B, Cc, Fr, H, W = x_in.shape
-    if not (x_in.is_contiguous() and x_out.is_contiguous() and x_last.is_contiguous() and x_out.shape == x_in.shape
-            and x_last.shape == x_in.shape and noise_pred.is_contiguous() and noise_pred.numel() == n_branch * x_in.numel()):
-        raise ValueError("guided_unipc: contiguous x_in / x_out / x_last of one shape and noise_pred of n_branch times their size")
+    (B, Cc, Fr, HW), nh, idx, (wcs, wps) = _step_args("guided_unipc", noise_pred, n_branch, (x_in, x_out, x_last), hist, store_slot,
+                                                      hist_idx, wc=wc, wp=wp)
     nbytes = x_in.numel() * 4
     if any(abs(x_last.data_ptr() - t.data_ptr()) < nbytes for t in (x_in, x_out)):
         raise ValueError("guided_unipc: x_last must not overlap x_in or x_out")
-    nh = len(hist_idx)
-    if nh > 4 or len(wc) != nh or len(wp) != nh:
-        raise ValueError("guided_unipc: at most 4 history entries, with one wc and one wp weight each")
-    slots = [s for s in (store_slot, *hist_idx) if s >= 0]
-    if slots and (hist is None or not hist.is_contiguous() or hist.dtype != F32 or hist.device != x_in.device
-                  or tuple(hist.shape[1:]) != tuple(x_in.shape) or max(slots) >= hist.shape[0] or min(hist_idx, default=0) < 0):
-        raise ValueError(f"guided_unipc: slots {slots} need a contiguous f32 hist of shape (> {max(slots)}, {tuple(x_in.shape)})")
-    idx = (C.c_int32 * 4)(*(list(hist_idx) + [0] * (4 - nh)))
-    wcs = (C.c_float * 4)(*(list(wc) + [0.0] * (4 - nh)))
-    wps = (C.c_float * 4)(*(list(wp) + [0.0] * (4 - nh)))
     check(_lib.lib().avsd_guided_unipc(_p(noise_pred), n_branch, float(g), float(g2), _p(hist), store_slot, idx, wcs, wps, nh,
                                        _p(x_in), _p(x_out), _p(x_last), int(bool(use_corrector)), float(s_x), float(s_e),
-                                       float(cc_last), float(cc_cur), float(cp_x), float(cp_cur), B, Cc, Fr, H * W, _stream()),
+                                       float(cc_last), float(cc_cur), float(cp_x), float(cp_cur), B, Cc, Fr, HW, _stream()),
           "avsd_guided_unipc")
 
 

@@ -26,7 +26,7 @@ import torch
 from . import dist as adist
 from .conditioning import AUDIO_TOKENS, audio_segment_mask
 from .engine import DenoiseEngine
-from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler, PNDMScheduler, UniPCMultistepScheduler
+from .schedulers import PNDMScheduler
 from .unet import AudioUNet3DConditionModel
 from .vae import AutoencoderKL
 from .audio_features import AudioMelspectrogramExtractor
@@ -198,8 +198,7 @@ class AudioCondAnimationPipeline:
         latents = self.prepare_video_latents(image_latents, self.unet.config.in_channels, video_length, height, width, device,
                                              f32, generator, noise)                                      # (b, 4, f, h, w)
 
-        if self.use_engine and isinstance(self.scheduler, (PNDMScheduler, DDIMScheduler, DPMSolverMultistepScheduler,
-                                                               UniPCMultistepScheduler)):
+        if self.use_engine and self._scheduler_plans():
             eng = self._engine_for(audio_guidance_scale, text_guidance_scale)
             self.unet.set_conditioning(text, audio, masks, video_length)      # already in the CFG branch order of :150-155,:186-194
             eng.prepare(latents, num_inference_steps)
@@ -220,6 +219,10 @@ class AudioCondAnimationPipeline:
         videos = self.decode_latents(latents.permute(0, 2, 1, 3, 4).reshape(b * f, c, h, w))
         videos = videos.reshape(b, f, *videos.shape[1:])
         return {"videos": videos} if return_dict else videos
+
+    def _scheduler_plans(self) -> bool:
+        """the DenoiseEngine can run this scheduler: it plans its steps (schedulers.py); any other object takes the reference-style loop"""
+        return hasattr(self.scheduler, "plan_step") and hasattr(self.scheduler, "num_forwards")
 
     def _engine_for(self, audio_guidance_scale: float, text_guidance_scale: float) -> DenoiseEngine:
         ekey = (id(self.unet), id(self.scheduler), float(audio_guidance_scale), float(text_guidance_scale))
@@ -264,7 +267,7 @@ class AudioCondAnimationPipeline:
             raise ValueError(f"animate_track: handover must be 'latent' or 'pixel', got {handover!r}")
         if output_type not in ("uint8", "uint8_device"):
             raise ValueError(f"animate_track: output_type must be 'uint8' or 'uint8_device', got {output_type!r}")
-        if not isinstance(self.scheduler, (PNDMScheduler, DDIMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler)):
+        if not self._scheduler_plans():
             raise ValueError(f"animate_track: runs on the DenoiseEngine, which has no plan for {type(self.scheduler).__name__}")
         if image_latents is not None:
             if image_latents.dim() == 3:

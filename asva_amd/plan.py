@@ -218,42 +218,12 @@ class Recorder:
 
 
 def export_steps(path: str, timesteps, plans) -> None:
-    """The scalar schedule of a denoising run (schedulers.plan_step: DDIM / PLMS coefficients of avsd_guided_step) as the
-    binary table tools/plan_host.cpp reads: per step  f32 t, ca, cb, w_cur; i32 store_slot, n_hist, save_sample, use_saved;
-    i32 hist_idx[4]; f32 hist_w[4]."""
+    """The scalar schedule of a denoising run (schedulers.plan_step) as the binary table tools/plan_host.cpp reads: one
+    `plan.record(t)` per step.  The plan type decides the line's layout and which plan_host command reads it (StepPlan:
+    `denoise`, MultistepPlan: `denoise_ms`, UniPCPlan: `denoise_unipc`)."""
     with open(path, "wb") as f:
         for t, p in zip(timesteps, plans):
-            idx = list(p.hist_idx) + [0] * (4 - len(p.hist_idx))
-            w = list(p.hist_w) + [0.0] * (4 - len(p.hist_w))
-            f.write(struct.pack("<4f4i4i4f", float(t), float(p.ca), float(p.cb), float(p.w_cur), int(p.store_slot), len(p.hist_idx),
-                                int(p.save_sample), int(p.use_saved_sample), *[int(i) for i in idx], *[float(x) for x in w]))
-
-
-def export_multistep_steps(path: str, timesteps, plans) -> None:
-    """The scalar schedule of a DPM-Solver++ run (schedulers.MultistepPlan: coefficients of avsd_guided_multistep) as the binary
-    table tools/plan_host.cpp's `denoise_ms` reads: per step  f32 t, ca, c_cur, s_x, s_e; i32 store_slot, n_hist; i32 hist_idx[4];
-    f32 hist_w[4]."""
-    with open(path, "wb") as f:
-        for t, p in zip(timesteps, plans):
-            idx = list(p.hist_idx) + [0] * (4 - len(p.hist_idx))
-            w = list(p.hist_w) + [0.0] * (4 - len(p.hist_w))
-            f.write(struct.pack("<5f2i4i4f", float(t), float(p.ca), float(p.c_cur), float(p.s_x), float(p.s_e), int(p.store_slot),
-                                len(p.hist_idx), *[int(i) for i in idx], *[float(x) for x in w]))
-
-
-def export_unipc_steps(path: str, timesteps, plans) -> None:
-    """The scalar schedule of a UniPC run (schedulers.UniPCPlan: coefficients of avsd_guided_unipc) as the binary table
-    tools/plan_host.cpp's `denoise_unipc` reads: per step  f32 t, s_x, s_e, cc_last, cc_cur, cp_x, cp_cur; i32 use_corrector,
-    store_slot, n_hist; i32 hist_idx[4]; f32 wc[4]; f32 wp[4]  (88 bytes)."""
-    with open(path, "wb") as f:
-        for t, p in zip(timesteps, plans):
-            nh = len(p.hist_idx)
-            idx = list(p.hist_idx) + [0] * (4 - nh)
-            wc = list(p.wc) + [0.0] * (4 - nh)
-            wp = list(p.wp) + [0.0] * (4 - nh)
-            f.write(struct.pack("<7f3i4i8f", float(t), float(p.s_x), float(p.s_e), float(p.cc_last), float(p.cc_cur), float(p.cp_x),
-                                float(p.cp_cur), int(p.use_corrector), int(p.store_slot), nh, *[int(i) for i in idx],
-                                *[float(x) for x in wc], *[float(x) for x in wp]))
+            f.write(p.record(t))
 
 
 class Bundle:

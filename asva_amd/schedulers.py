@@ -1,27 +1,26 @@
-"""PNDM (PLMS) and DDIM schedulers for the denoising loop — host-side scalar schedule + one fused device
-kernel per step (avsd_guided_step: guidance combine, multistep blend, latent update, frame-0 pinning).
+"""The four samplers of the denoising loop: PNDMScheduler (PLMS) and DDIMScheduler on `_Base`, DPMSolverMultistepScheduler
+(DPM-Solver++ 1M / 2M / 3M) and UniPCMultistepScheduler (predictor plus a corrector that reuses the next step's model output) on
+`_Multistep`, all under `_Scheduler`.  Each is a host-side scalar schedule in float64 plus ONE fused device kernel per step.
 
 The reference takes its scheduler from diffusers (PNDMScheduler.from_pretrained(sd15, "scheduler"),
-pipeline_audio_cond_animation.py:511; called at :325-327,337,364).  diffusers 0.29.2 is not vendored in the
-reference nor installed here, so the update rules are restated from its published algorithm
-(`PNDMScheduler.set_timesteps/step_plms/_get_prev_sample`, `DDIMScheduler.set_timesteps/step`) for the SD1.5
-scheduler_config.json: scaled_linear betas 0.00085..0.012 over 1000 steps, steps_offset 1, skip_prk_steps
-true, set_alpha_to_one false, epsilon prediction, "leading" timestep spacing.
+pipeline_audio_cond_animation.py:511; called at :325-327,337,364).  diffusers 0.29.2 is not vendored in the reference nor
+installed here, so the update rules are restated from its published algorithms (each class names the functions it restates).
+PNDM / DDIM cover the SD1.5 scheduler_config.json: scaled_linear betas 0.00085..0.012 over 1000 steps, steps_offset 1,
+skip_prk_steps true, set_alpha_to_one false, epsilon prediction, "leading" timestep spacing.
 
-Both classes also expose the object protocol the reference pipeline uses (`set_timesteps`, `timesteps`,
-`init_noise_sigma`, `scale_model_input`, `step(...).prev_sample`) so they drop into
-AudioCondAnimationPipeline; the fast path (`plan_step` + `ops.guided_step`) folds guidance and the update
-into one launch and keeps the eps history on the device.
-
-DPMSolverMultistepScheduler (DPM-Solver++ 1M / 2M / 3M, restated from diffusers 0.29.2 the same way) offers the same two
-forms; its fast path is `plan_step` + `ops.guided_multistep` (avsd_guided_multistep), whose ring holds data predictions.
-
-UniPCMultistepScheduler (UniPC: DPM-Solver++-style predictor plus a corrector that reuses the next step's model output) has
-the same two forms; its fast path is `plan_step` + `ops.guided_unipc` (avsd_guided_unipc): corrector and predictor in one launch.
+Every class has two forms of the same arithmetic:
+  * the object protocol of the reference pipeline (`set_timesteps`, `timesteps`, `init_noise_sigma`, `scale_model_input`,
+    `step(...).prev_sample`), tensor-level on any device, so that it drops into AudioCondAnimationPipeline;
+  * the fast path: `plan_step(i)` turns step i into a plan of scalars (StepPlan, MultistepPlan or UniPCPlan), and the plan is the
+    seam to everything below it.  `plan.launch(ops, ...)` makes the one kernel launch that folds guidance, the update and frame-0
+    pinning (ops.guided_step / guided_multistep / guided_unipc; the history ring stays on the device), and `plan.record(t)` is
+    the plan's line in the table a Python-free host replays (asva_amd/plan.py, tools/plan_host.cpp).  DenoiseEngine, the
+    pipeline and the exporter know a scheduler only through `plan_step` / `num_forwards` and a plan only through these two.
 """
 from __future__ import annotations
 
 import math
+import struct
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
 
@@ -42,6 +41,17 @@ def alphas_cumprod(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012,
     return torch.cumprod(1.0 - betas, dim=0).numpy().astype(np.float64)
 
 
+def _pad4(values, zero) -> list:
+    """a ring table as the kernels and the plan tables take it: 4 entries"""
+    return list(values) + [zero] * (4 - len(values))
+
+
+# A plan is one scheduler step as scalars.  `launch(ops, noise, n_branch, g, g2, x, bufs)` runs it in place on the latents `x` with
+# the noise prediction of the CFG batch and its guidance mix (DenoiseEngine.__init__); `bufs` holds the ring `_hist`, the PLMS
+# copy `_saved` and UniPC's corrected sample `_x_last` (the engine itself).  `ops` is passed in so that whoever drives the plan
+# decides which implementation of the kernel contracts it runs on.  `record(t)` is the step's line in the binary table
+# plan.export_steps writes and tools/plan_host.cpp reads.
+
 @dataclass
 class StepPlan:
     """Everything avsd_guided_step needs for one scheduler step."""
@@ -53,6 +63,19 @@ class StepPlan:
     hist_w: Tuple[float, ...] = ()
     use_saved_sample: bool = False    # PLMS second step restarts from the sample saved at step 0
     save_sample: bool = False         # PLMS first step saves its input sample
+
+    def launch(self, ops, noise, n_branch, g, g2, x, bufs) -> None:
+        if self.save_sample:
+            ops.copy(x, bufs._saved)
+        ops.guided_step(noise, n_branch, g, bufs._saved if self.use_saved_sample else x, x, self.ca, self.cb, eps_hist=bufs._hist,
+                        store_slot=self.store_slot, w_cur=self.w_cur, hist_idx=self.hist_idx, w=self.hist_w, g2=g2)
+
+    def record(self, t) -> bytes:
+        """f32 t, ca, cb, w_cur; i32 store_slot, n_hist, save_sample, use_saved; i32 hist_idx[4]; f32 hist_w[4]  (64 bytes; plan_host's
+        `denoise`)"""
+        return struct.pack("<4f4i4i4f", float(t), float(self.ca), float(self.cb), float(self.w_cur), int(self.store_slot),
+                           len(self.hist_idx), int(self.save_sample), int(self.use_saved_sample), *_pad4(self.hist_idx, 0),
+                           *_pad4(self.hist_w, 0.0))
 
 
 @dataclass
@@ -66,6 +89,15 @@ class MultistepPlan:
     store_slot: int = -1      # ring slot to store d in (-1: do not store)
     hist_idx: Tuple[int, ...] = ()
     hist_w: Tuple[float, ...] = ()
+
+    def launch(self, ops, noise, n_branch, g, g2, x, bufs) -> None:
+        ops.guided_multistep(noise, n_branch, g, x, x, self.ca, self.c_cur, self.s_x, self.s_e, hist=bufs._hist,
+                             store_slot=self.store_slot, hist_idx=self.hist_idx, w=self.hist_w, g2=g2)
+
+    def record(self, t) -> bytes:
+        """f32 t, ca, c_cur, s_x, s_e; i32 store_slot, n_hist; i32 hist_idx[4]; f32 hist_w[4]  (60 bytes; plan_host's `denoise_ms`)"""
+        return struct.pack("<5f2i4i4f", float(t), float(self.ca), float(self.c_cur), float(self.s_x), float(self.s_e),
+                           int(self.store_slot), len(self.hist_idx), *_pad4(self.hist_idx, 0), *_pad4(self.hist_w, 0.0))
 
 
 @dataclass
@@ -87,6 +119,18 @@ class UniPCPlan:
     wp: Tuple[float, ...] = ()            # ... and for the predictor
     order: int = 1                        # order of this step's predictor
     corrector_order: int = 0              # order of this step's corrector (0: none)
+
+    def launch(self, ops, noise, n_branch, g, g2, x, bufs) -> None:
+        ops.guided_unipc(noise, n_branch, g, x, x, bufs._x_last, self.use_corrector, self.s_x, self.s_e, self.cc_last, self.cc_cur,
+                         self.cp_x, self.cp_cur, hist=bufs._hist, store_slot=self.store_slot, hist_idx=self.hist_idx, wc=self.wc,
+                         wp=self.wp, g2=g2)
+
+    def record(self, t) -> bytes:
+        """f32 t, s_x, s_e, cc_last, cc_cur, cp_x, cp_cur; i32 use_corrector, store_slot, n_hist; i32 hist_idx[4]; f32 wc[4]; f32 wp[4]
+        (88 bytes; plan_host's `denoise_unipc`)"""
+        return struct.pack("<7f3i4i8f", float(t), float(self.s_x), float(self.s_e), float(self.cc_last), float(self.cc_cur),
+                           float(self.cp_x), float(self.cp_cur), int(self.use_corrector), int(self.store_slot), len(self.hist_idx),
+                           *_pad4(self.hist_idx, 0), *_pad4(self.wc, 0.0), *_pad4(self.wp, 0.0))
 
 
 class _Output:
@@ -145,10 +189,34 @@ class _ForwardProcess:
         return self._forward_process(sample, noise, timesteps, velocity=True)
 
 
-class _Base(_ForwardProcess):
+class _Scheduler(_ForwardProcess):
+    """What the pipeline and the engine ask of every scheduler besides `set_timesteps`, `plan_step` and `step`."""
     order = 1
     init_noise_sigma = 1.0
 
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    def num_forwards(self) -> int:
+        return len(self._ts)
+
+    @classmethod
+    def from_pretrained(cls, path: str, subfolder: Optional[str] = None):
+        return cls.from_config(_read_config(path, subfolder))
+
+    @classmethod
+    def from_config(cls, config, **overrides):
+        """diffusers' `Scheduler.from_config(pipe.scheduler.config)`: another scheduler's configuration.  Private keys are dropped,
+        `_adopt` translates what this class spells differently, and the constructor accepts and ignores the other class's own
+        keys (PNDM's skip_prk_steps, DPM-Solver++'s algorithm_type, ...) where diffusers does."""
+        return cls(**{**cls._adopt({k: v for k, v in dict(config).items() if not k.startswith("_")}), **overrides})
+
+    @staticmethod
+    def _adopt(cfg: dict) -> dict:
+        return cfg
+
+
+class _Base(_Scheduler):
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
                  steps_offset=1, set_alpha_to_one=False, prediction_type="epsilon", timestep_spacing="leading",
                  trained_betas=None, clip_sample=False, thresholding=False, rescale_betas_zero_snr=False, **unknown):
@@ -173,13 +241,6 @@ class _Base(_ForwardProcess):
                            beta_schedule=beta_schedule, steps_offset=steps_offset, set_alpha_to_one=set_alpha_to_one,
                            prediction_type=prediction_type, timestep_spacing=timestep_spacing)
 
-    def scale_model_input(self, sample, timestep=None):
-        return sample
-
-    @classmethod
-    def from_pretrained(cls, path: str, subfolder: Optional[str] = None):
-        return cls(**_read_config(path, subfolder))
-
     def _acp(self, t: int) -> float:
         return float(self.acp[t]) if t >= 0 else self.final_alpha_cumprod
 
@@ -193,9 +254,6 @@ class DDIMScheduler(_Base):
         ts = (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64) + self.steps_offset
         self._ts = [int(t) for t in ts]
         self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
-
-    def num_forwards(self) -> int:
-        return len(self._ts)
 
     def plan_step(self, i: int) -> StepPlan:
         t = self._ts[i]
@@ -244,9 +302,6 @@ class PNDMScheduler(_Base):
         self.ets: List[torch.Tensor] = []
         self.counter = 0
         self.cur_sample = None
-
-    def num_forwards(self) -> int:
-        return len(self._ts)
 
     def _coeffs(self, t: int, prev: int) -> Tuple[float, float]:
         a, ap = self._acp(t), self._acp(prev)
@@ -310,8 +365,66 @@ class PNDMScheduler(_Base):
         return _Output(prev_sample) if return_dict else (prev_sample,)
 
 
-class _SigmaTables(_ForwardProcess):
-    """What DPMSolverMultistepScheduler and UniPCMultistepScheduler share: the timestep / sigma tables of a run."""
+class _Multistep(_Scheduler):
+    """What DPMSolverMultistepScheduler and UniPCMultistepScheduler share: the options both take, the timestep / sigma tables of a
+    run, the data prediction x0 = (x - sigma_t eps) / alpha_t, and the bookkeeping of the object protocol.  A subclass names its
+    SOLVER_TYPES, the other classes' keys it ignores (KNOWN_INERT, as diffusers ignores them) and the order of its `config`."""
+
+    SOLVER_TYPES: Tuple[str, ...] = ()
+    KNOWN_INERT: frozenset = frozenset()
+    CONFIG_KEYS: Tuple[str, ...] = ()
+
+    def __init__(self, num_train_timesteps, beta_start, beta_end, beta_schedule, solver_order, solver_type, lower_order_final,
+                 use_karras_sigmas, final_sigmas_type, timestep_spacing, steps_offset, refused: Optional[str], unknown: dict, **own):
+        """`refused`: the subclass's message when one of its options that change the samples is set; `own`: its own `config` items"""
+        if solver_order not in (1, 2, 3) or solver_type not in self.SOLVER_TYPES:
+            raise NotImplementedError(f"solver_order {solver_order!r} / solver_type {solver_type!r}: orders 1-3, "
+                                      f"{' or '.join(self.SOLVER_TYPES)}")
+        if final_sigmas_type not in ("zero", "sigma_min") or timestep_spacing not in ("linspace", "leading", "trailing"):
+            raise NotImplementedError(f"final_sigmas_type {final_sigmas_type!r} / timestep_spacing {timestep_spacing!r}")
+        if refused:
+            raise NotImplementedError(refused)
+        bad = sorted(k for k in unknown if not k.startswith("_") and k not in self.KNOWN_INERT)
+        if bad:
+            raise NotImplementedError(f"unknown scheduler options {bad}")
+        self.num_train_timesteps = num_train_timesteps
+        self.solver_order, self.solver_type, self.lower_order_final = solver_order, solver_type, lower_order_final
+        self.final_sigmas_type, self.use_karras_sigmas = final_sigmas_type, use_karras_sigmas
+        self.timestep_spacing, self.steps_offset = timestep_spacing, steps_offset
+        self.acp = alphas_cumprod(num_train_timesteps, beta_start, beta_end, beta_schedule)
+        self.num_inference_steps: Optional[int] = None
+        self.timesteps: Optional[torch.Tensor] = None
+        self.sigmas: Optional[np.ndarray] = None
+        items = dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end, beta_schedule=beta_schedule,
+                     solver_order=solver_order, prediction_type="epsilon", solver_type=solver_type,
+                     lower_order_final=lower_order_final, use_karras_sigmas=use_karras_sigmas, final_sigmas_type=final_sigmas_type,
+                     timestep_spacing=timestep_spacing, steps_offset=steps_offset, **own)
+        self.config = {k: items[k] for k in self.CONFIG_KEYS}
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        self._build_tables(num_inference_steps, device)
+        # object-protocol state
+        self.model_outputs: List[Optional[torch.Tensor]] = [None] * self.solver_order
+        self.lower_order_nums = 0
+        self._step_index: Optional[int] = None
+
+    def _scales(self, i: int) -> Tuple[float, float]:
+        """(s_x, s_e) of a plan: the data prediction of step i is s_x * x + s_e * eps"""
+        alpha_s, sigma_s = self._alpha_sigma(float(self.sigmas[i]))
+        return 1.0 / alpha_s, -sigma_s / alpha_s
+
+    def _begin_step(self, model_output, timestep, sample):
+        """object protocol: the index of this `step()` call and its data prediction, from the sample the model saw"""
+        if self._step_index is None:
+            hits = [j for j, t in enumerate(self._ts) if t == int(timestep)]
+            self._step_index = (hits[1] if len(hits) > 1 else hits[0]) if hits else len(self._ts) - 1
+        alpha_s, sigma_s = self._alpha_sigma(float(self.sigmas[self._step_index]))
+        return self._step_index, (sample - sigma_s * model_output) / alpha_s
+
+    def _end_step(self, prev_sample, return_dict):
+        self.lower_order_nums = min(self.lower_order_nums + 1, self.solver_order)
+        self._step_index += 1
+        return _Output(prev_sample) if return_dict else (prev_sample,)
 
     def _build_tables(self, num_inference_steps: int, device=None):
         """timesteps and the float32-rounded sigma table (n + 1 entries: the last one is the final sigma) from timestep_spacing,
@@ -355,7 +468,7 @@ class _SigmaTables(_ForwardProcess):
         return math.log(alpha_t) - math.log(sigma_t)
 
 
-class DPMSolverMultistepScheduler(_SigmaTables):
+class DPMSolverMultistepScheduler(_Multistep):
     """DPM-Solver++ (Lu et al. 2022, arXiv:2211.01095), multistep, orders 1-3, restated from diffusers 0.29.2's
     `DPMSolverMultistepScheduler` (`set_timesteps`, `convert_model_output`, `dpm_solver_first_order_update`,
     `multistep_dpm_solver_second_order_update`, `multistep_dpm_solver_third_order_update`, `step`) for the deterministic
@@ -386,8 +499,12 @@ class DPMSolverMultistepScheduler(_SigmaTables):
     euler_at_final, lambda_min_clipped, Lu lambdas, rescale_betas_zero_snr, trained_betas) raises NotImplementedError.
     """
 
-    order = 1
-    init_noise_sigma = 1.0
+    SOLVER_TYPES = ("midpoint", "heun")
+    # keys of the SD1.5 PNDM / DDIM configurations that DPM-Solver++ does not have
+    KNOWN_INERT = frozenset({"skip_prk_steps", "set_alpha_to_one", "clip_sample", "clip_sample_range"})
+    CONFIG_KEYS = ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "solver_order", "prediction_type",
+                   "algorithm_type", "solver_type", "lower_order_final", "use_karras_sigmas", "final_sigmas_type", "timestep_spacing",
+                   "steps_offset")
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
                  trained_betas=None, solver_order=2, prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995,
@@ -397,55 +514,12 @@ class DPMSolverMultistepScheduler(_SigmaTables):
                  rescale_betas_zero_snr=False, **unknown):
         if algorithm_type != "dpmsolver++" or prediction_type != "epsilon":
             raise NotImplementedError("only algorithm_type='dpmsolver++' with prediction_type='epsilon' is restated")
-        if solver_order not in (1, 2, 3) or solver_type not in ("midpoint", "heun"):
-            raise NotImplementedError(f"solver_order {solver_order!r} / solver_type {solver_type!r}: orders 1-3, midpoint or heun")
-        if final_sigmas_type not in ("zero", "sigma_min") or timestep_spacing not in ("linspace", "leading", "trailing"):
-            raise NotImplementedError(f"final_sigmas_type {final_sigmas_type!r} / timestep_spacing {timestep_spacing!r}")
-        if (thresholding or euler_at_final or use_lu_lambdas or variance_type is not None or rescale_betas_zero_snr
-                or trained_betas is not None or lambda_min_clipped != -float("inf")):
-            raise NotImplementedError("thresholding / euler_at_final / use_lu_lambdas / variance_type / lambda_min_clipped / "
-                                      "rescale_betas_zero_snr / trained_betas are not restated")
-        # keys of the SD1.5 PNDM / DDIM configurations that DPM-Solver++ does not have (diffusers ignores them as well)
-        known_inert = {"skip_prk_steps", "set_alpha_to_one", "clip_sample", "clip_sample_range"}
-        bad = sorted(k for k in unknown if not k.startswith("_") and k not in known_inert)
-        if bad:
-            raise NotImplementedError(f"unknown scheduler options {bad}")
-        self.num_train_timesteps = num_train_timesteps
-        self.solver_order, self.solver_type, self.lower_order_final = solver_order, solver_type, lower_order_final
-        self.final_sigmas_type, self.use_karras_sigmas = final_sigmas_type, use_karras_sigmas
-        self.timestep_spacing, self.steps_offset = timestep_spacing, steps_offset
-        self.acp = alphas_cumprod(num_train_timesteps, beta_start, beta_end, beta_schedule)
-        self.num_inference_steps: Optional[int] = None
-        self.timesteps: Optional[torch.Tensor] = None
-        self.sigmas: Optional[np.ndarray] = None
-        self.config = dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
-                           beta_schedule=beta_schedule, solver_order=solver_order, prediction_type=prediction_type,
-                           algorithm_type=algorithm_type, solver_type=solver_type, lower_order_final=lower_order_final,
-                           use_karras_sigmas=use_karras_sigmas, final_sigmas_type=final_sigmas_type,
-                           timestep_spacing=timestep_spacing, steps_offset=steps_offset)
-
-    @classmethod
-    def from_pretrained(cls, path: str, subfolder: Optional[str] = None):
-        return cls(**_read_config(path, subfolder))
-
-    @classmethod
-    def from_config(cls, config, **overrides):
-        """diffusers' `DPMSolverMultistepScheduler.from_config(pipe.scheduler.config)`: another scheduler's configuration,
-        with its own keys (PNDM's skip_prk_steps, ...) accepted and ignored."""
-        return cls(**{k: v for k, v in {**dict(config), **overrides}.items() if not k.startswith("_")})
-
-    def scale_model_input(self, sample, timestep=None):
-        return sample
-
-    def set_timesteps(self, num_inference_steps: int, device=None):
-        self._build_tables(num_inference_steps, device)
-        # object-protocol state
-        self.model_outputs: List[Optional[torch.Tensor]] = [None] * self.solver_order
-        self.lower_order_nums = 0
-        self._step_index: Optional[int] = None
-
-    def num_forwards(self) -> int:
-        return len(self._ts)
+        refused = (thresholding or euler_at_final or use_lu_lambdas or variance_type is not None or rescale_betas_zero_snr
+                   or trained_betas is not None or lambda_min_clipped != -float("inf"))
+        super().__init__(num_train_timesteps, beta_start, beta_end, beta_schedule, solver_order, solver_type, lower_order_final,
+                         use_karras_sigmas, final_sigmas_type, timestep_spacing, steps_offset,
+                         refused and "thresholding / euler_at_final / use_lu_lambdas / variance_type / lambda_min_clipped / "
+                                     "rescale_betas_zero_snr / trained_betas are not restated", unknown, algorithm_type=algorithm_type)
 
     def _coeffs(self, i: int):
         """x' = ca x + c0 D0 + c1 D1 + c2 D2 for the step sigmas[i] -> sigmas[i + 1], and the ratios r0 = h_0 / h, r1 = h_1 / h of
@@ -473,7 +547,6 @@ class DPMSolverMultistepScheduler(_SigmaTables):
         """Step i as coefficients of avsd_guided_multistep.  The data prediction of step j lives in ring slot j % solver_order;
         it is stored only when a later step reads it."""
         last_first, second_last = self._lower_order(i)
-        alpha_s, sigma_s = self._alpha_sigma(float(self.sigmas[i]))
         ca, c0, c1, c2, r0, r1 = self._coeffs(i)
         if self.solver_order == 1 or i < 1 or last_first or c1 is None:
             k = 1
@@ -494,17 +567,13 @@ class DPMSolverMultistepScheduler(_SigmaTables):
             cur = c0 + c1 * (1 + q) * a + c2 * p * a
             idx = (slot(i - 1), slot(i - 2))
             w = (-c1 * ((1 + q) * a + q * b) - c2 * p * (a + b), c1 * q * b + c2 * p * b)
-        return MultistepPlan(ca=ca, c_cur=cur, s_x=1.0 / alpha_s, s_e=-sigma_s / alpha_s, store_slot=store, hist_idx=idx, hist_w=w)
+        s_x, s_e = self._scales(i)
+        return MultistepPlan(ca=ca, c_cur=cur, s_x=s_x, s_e=s_e, store_slot=store, hist_idx=idx, hist_w=w)
 
     # object protocol (tensor-level, any device): diffusers' step, written over the data predictions themselves
     def step(self, model_output, timestep, sample, return_dict=True, **_):
-        if self._step_index is None:
-            hits = [j for j, t in enumerate(self._ts) if t == int(timestep)]
-            self._step_index = (hits[1] if len(hits) > 1 else hits[0]) if hits else len(self._ts) - 1
-        i = self._step_index
+        i, x0 = self._begin_step(model_output, timestep, sample)
         last_first, second_last = self._lower_order(i)
-        alpha_s, sigma_s = self._alpha_sigma(float(self.sigmas[i]))
-        x0 = (sample - sigma_s * model_output) / alpha_s
         self.model_outputs = self.model_outputs[1:] + [x0]
         m = self.model_outputs
         ca, c0, c1, c2, r0, r1 = self._coeffs(i)
@@ -518,12 +587,10 @@ class DPMSolverMultistepScheduler(_SigmaTables):
             D1 = D1_0 + (r0 / (r0 + r1)) * (D1_0 - D1_1)
             D2 = (1.0 / (r0 + r1)) * (D1_0 - D1_1)
             prev_sample = ca * sample + c0 * m[-1] + c1 * D1 + c2 * D2
-        self.lower_order_nums = min(self.lower_order_nums + 1, self.solver_order)
-        self._step_index += 1
-        return _Output(prev_sample) if return_dict else (prev_sample,)
+        return self._end_step(prev_sample, return_dict)
 
 
-class UniPCMultistepScheduler(_SigmaTables):
+class UniPCMultistepScheduler(_Multistep):
     """UniPC (Zhao et al. 2023, arXiv:2302.04867): a unified predictor-corrector on the data predictions, orders 1-3, variants
     bh1 / bh2, restated from the paper's update (its Algorithm 5-8 with B(h) = h or e^h - 1) and from diffusers 0.29.2's
     `UniPCMultistepScheduler` (`set_timesteps`, `convert_model_output`, `multistep_uni_p_bh_update`,
@@ -571,8 +638,13 @@ class UniPCMultistepScheduler(_SigmaTables):
     rescale_betas_zero_snr, trained_betas, other final_sigmas_type) raises NotImplementedError, and so do unknown keys.
     """
 
-    order = 1
-    init_noise_sigma = 1.0
+    SOLVER_TYPES = ("bh1", "bh2")
+    # keys of the PNDM / DDIM / DPM-Solver++ configurations that UniPC does not have
+    KNOWN_INERT = frozenset({"skip_prk_steps", "set_alpha_to_one", "clip_sample", "clip_sample_range", "algorithm_type",
+                             "euler_at_final", "use_lu_lambdas", "lambda_min_clipped", "variance_type"})
+    CONFIG_KEYS = ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "solver_order", "prediction_type", "predict_x0",
+                   "solver_type", "lower_order_final", "disable_corrector", "use_karras_sigmas", "final_sigmas_type",
+                   "timestep_spacing", "steps_offset")
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
                  trained_betas=None, solver_order=2, prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995,
@@ -581,60 +653,22 @@ class UniPCMultistepScheduler(_SigmaTables):
                  rescale_betas_zero_snr=False, **unknown):
         if not predict_x0 or prediction_type != "epsilon":
             raise NotImplementedError("only predict_x0=True with prediction_type='epsilon' is restated")
-        if solver_order not in (1, 2, 3) or solver_type not in ("bh1", "bh2"):
-            raise NotImplementedError(f"solver_order {solver_order!r} / solver_type {solver_type!r}: orders 1-3, bh1 or bh2")
-        if final_sigmas_type not in ("zero", "sigma_min") or timestep_spacing not in ("linspace", "leading", "trailing"):
-            raise NotImplementedError(f"final_sigmas_type {final_sigmas_type!r} / timestep_spacing {timestep_spacing!r}")
-        if thresholding or solver_p is not None or rescale_betas_zero_snr or trained_betas is not None:
-            raise NotImplementedError("thresholding / solver_p / rescale_betas_zero_snr / trained_betas are not restated")
-        # keys of the PNDM / DDIM / DPM-Solver++ configurations that UniPC does not have (diffusers ignores them as well)
-        known_inert = {"skip_prk_steps", "set_alpha_to_one", "clip_sample", "clip_sample_range", "algorithm_type", "euler_at_final",
-                       "use_lu_lambdas", "lambda_min_clipped", "variance_type"}
-        bad = sorted(k for k in unknown if not k.startswith("_") and k not in known_inert)
-        if bad:
-            raise NotImplementedError(f"unknown scheduler options {bad}")
-        self.num_train_timesteps = num_train_timesteps
-        self.solver_order, self.solver_type, self.lower_order_final = solver_order, solver_type, lower_order_final
+        refused = thresholding or solver_p is not None or rescale_betas_zero_snr or trained_betas is not None
         self.disable_corrector = [int(i) for i in disable_corrector]
-        self.final_sigmas_type, self.use_karras_sigmas = final_sigmas_type, use_karras_sigmas
-        self.timestep_spacing, self.steps_offset = timestep_spacing, steps_offset
-        self.acp = alphas_cumprod(num_train_timesteps, beta_start, beta_end, beta_schedule)
-        self.num_inference_steps: Optional[int] = None
-        self.timesteps: Optional[torch.Tensor] = None
-        self.sigmas: Optional[np.ndarray] = None
-        self.config = dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
-                           beta_schedule=beta_schedule, solver_order=solver_order, prediction_type=prediction_type,
-                           predict_x0=True, solver_type=solver_type, lower_order_final=lower_order_final,
-                           disable_corrector=list(self.disable_corrector), use_karras_sigmas=use_karras_sigmas,
-                           final_sigmas_type=final_sigmas_type, timestep_spacing=timestep_spacing, steps_offset=steps_offset)
+        super().__init__(num_train_timesteps, beta_start, beta_end, beta_schedule, solver_order, solver_type, lower_order_final,
+                         use_karras_sigmas, final_sigmas_type, timestep_spacing, steps_offset,
+                         refused and "thresholding / solver_p / rescale_betas_zero_snr / trained_betas are not restated", unknown,
+                         predict_x0=True, disable_corrector=list(self.disable_corrector))
 
-    @classmethod
-    def from_pretrained(cls, path: str, subfolder: Optional[str] = None):
-        return cls.from_config(_read_config(path, subfolder))
-
-    @classmethod
-    def from_config(cls, config, **overrides):
-        """diffusers' `UniPCMultistepScheduler.from_config(pipe.scheduler.config)`: another scheduler's configuration, with its own
-        keys (PNDM's skip_prk_steps, DPM-Solver++'s algorithm_type, ...) accepted and ignored and its solver_type mapped to bh2."""
-        cfg = {k: v for k, v in dict(config).items() if not k.startswith("_")}
-        if cfg.get("solver_type") in ("midpoint", "heun", "logrho"):
-            cfg["solver_type"] = "bh2"
-        return cls(**{**cfg, **overrides})
-
-    def scale_model_input(self, sample, timestep=None):
-        return sample
+    @staticmethod
+    def _adopt(cfg: dict) -> dict:
+        """another class's solver_type (a DPM-Solver++ configuration's) becomes bh2, as in diffusers' constructor"""
+        return dict(cfg, solver_type="bh2") if cfg.get("solver_type") in ("midpoint", "heun", "logrho") else cfg
 
     def set_timesteps(self, num_inference_steps: int, device=None):
-        self._build_tables(num_inference_steps, device)
-        # object-protocol state
-        self.model_outputs: List[Optional[torch.Tensor]] = [None] * self.solver_order
+        super().set_timesteps(num_inference_steps, device)
         self.last_sample: Optional[torch.Tensor] = None
-        self.lower_order_nums = 0
         self.this_order = 0
-        self._step_index: Optional[int] = None
-
-    def num_forwards(self) -> int:
-        return len(self._ts)
 
     # ---- one update's scalars ---------------------------------------------------------------------------------------------
     def _update(self, s0: int, t: int, prev: Tuple[int, ...], corrector: bool):
@@ -690,8 +724,7 @@ class UniPCMultistepScheduler(_SigmaTables):
         """Step i as coefficients of avsd_guided_unipc: both updates folded into per-slot weights.  m_j lives in ring slot
         j % solver_order; m_i is stored (after the reads) only when a later step reads it."""
         n = len(self._ts)
-        alpha_s, sigma_s = self._alpha_sigma(float(self.sigmas[i]))
-        w = {}                                     # table entry j < i -> [corrector weight, predictor weight] of m_j
+        w = {}                                   # table entry j < i -> [corrector weight, predictor weight] of m_j
         cc_last = cc_cur = 0.0
         q = self._order(i - 1) if self._corrects(i) else 0
         if q:
@@ -714,9 +747,10 @@ class UniPCMultistepScheduler(_SigmaTables):
                 w.setdefault(i - k, [0.0, 0.0])[1] += ab * rhos[k - 1] / rks[k - 1]
         js = sorted(w, reverse=True)
         store = i % self.solver_order if any(i in self._reads(j) for j in range(i + 1, min(n, i + self.solver_order + 1))) else -1
-        return UniPCPlan(s_x=1.0 / alpha_s, s_e=-sigma_s / alpha_s, use_corrector=bool(q), cc_last=cc_last, cc_cur=cc_cur,
-                         cp_x=cp_x, cp_cur=cp_cur, store_slot=store, hist_idx=tuple(j % self.solver_order for j in js),
-                         wc=tuple(w[j][0] for j in js), wp=tuple(w[j][1] for j in js), order=p, corrector_order=q)
+        s_x, s_e = self._scales(i)
+        return UniPCPlan(s_x=s_x, s_e=s_e, use_corrector=bool(q), cc_last=cc_last, cc_cur=cc_cur, cp_x=cp_x, cp_cur=cp_cur,
+                         store_slot=store, hist_idx=tuple(j % self.solver_order for j in js), wc=tuple(w[j][0] for j in js),
+                         wp=tuple(w[j][1] for j in js), order=p, corrector_order=q)
 
     # object protocol (tensor-level, any device): diffusers' step, written over the differences D1_k = (m_k - m0) / r_k
     def _apply(self, u, x, m0, ms):
@@ -727,12 +761,7 @@ class UniPCMultistepScheduler(_SigmaTables):
         return out
 
     def step(self, model_output, timestep, sample, return_dict=True, **_):
-        if self._step_index is None:
-            hits = [j for j, t in enumerate(self._ts) if t == int(timestep)]
-            self._step_index = (hits[1] if len(hits) > 1 else hits[0]) if hits else len(self._ts) - 1
-        i = self._step_index
-        alpha_s, sigma_s = self._alpha_sigma(float(self.sigmas[i]))
-        m_t = (sample - sigma_s * model_output) / alpha_s          # from the uncorrected sample the model saw
+        i, m_t = self._begin_step(model_output, timestep, sample)   # from the uncorrected sample the model saw
         m = [v for v in self.model_outputs if v is not None]       # m_{i-1} last
         use_corrector = self._corrects(i) and self.last_sample is not None
         if use_corrector:
@@ -748,6 +777,4 @@ class UniPCMultistepScheduler(_SigmaTables):
         else:
             u = self._update(i, i + 1, tuple(i - k for k in range(1, self.this_order)), corrector=False)
             prev_sample = sample.clone() if u is None else self._apply(u, sample, m_t, [m[-1 - k] for k in range(1, self.this_order)])
-        self.lower_order_nums = min(self.lower_order_nums + 1, self.solver_order)
-        self._step_index += 1
-        return _Output(prev_sample) if return_dict else (prev_sample,)
+        return self._end_step(prev_sample, return_dict)

@@ -243,14 +243,14 @@ def test_config_from_pndm_config_and_from_pretrained(tmp_path):
 
 
 def test_step_table_writer(tmp_path):
-    """plan.export_multistep_steps: the table tools/plan_host.cpp's denoise_ms reads (60 bytes per step)"""
+    """plan.export_steps: the table tools/plan_host.cpp's denoise_ms reads (60 bytes per step)"""
     from asva_amd import plan
 
     s = _sched(solver_order=3)
     s.set_timesteps(7)
     plans = [s.plan_step(i) for i in range(7)]
     path = tmp_path / "steps_ms.bin"
-    plan.export_multistep_steps(str(path), s.timesteps.tolist(), plans)
+    plan.export_steps(str(path), s.timesteps.tolist(), plans)
     raw = path.read_bytes()
     assert len(raw) == 7 * 60
     for i, p in enumerate(plans):

@@ -149,7 +149,7 @@ def test_sd15_clip_through_pipeline_dpmsolver_20_steps():
 @pytest.mark.parametrize("graph", ["0", "1"])
 def test_cpp_host_runs_the_dpmsolver_loop_without_python(tmp_path, graph):
     """test_plan_gpu.py::test_cpp_host_runs_the_denoising_loop_without_python for DPM++ 2M, 20 steps: the table written by
-    plan.export_multistep_steps, plan_host's `denoise_ms` — latents byte-identical to the Python engine's"""
+    plan.export_steps, plan_host's `denoise_ms` — latents byte-identical to the Python engine's"""
     from asva_amd import _lib, build, plan
     from asva_amd.engine import DenoiseEngine
     from asva_amd.schedulers import DPMSolverMultistepScheduler
@@ -162,7 +162,7 @@ def test_cpp_host_runs_the_dpmsolver_loop_without_python(tmp_path, graph):
     eng.set_conditioning(g["text"][:1].cuda(), g["audio"][1:2].cuda(), g["audio"][:1].cuda(), g["mask"], lat0.shape[2])
     want = eng.run(lat0, 20)
     torch.cuda.synchronize()
-    plan.export_multistep_steps(str(tmp_path / "steps_ms.bin"), eng._ts.tolist(), eng._plans)
+    plan.export_steps(str(tmp_path / "steps_ms.bin"), eng._ts.tolist(), eng._plans)
     for name, tns in (("text", r["text"]), ("audio", r["audio"]), ("latents", lat0)):
         _bytes(tns).cpu().numpy().tofile(str(tmp_path / f"{name}.in"))
     b, c, f, h, w = r["shape"]

@@ -638,6 +638,25 @@ def test_guided_step(ops):
     assert torch.allclose(x2, ref2, atol=1e-5)
 
 
+def test_guided_step_refuses_bad_arguments(ops):
+    """the checks guided_multistep / guided_unipc make, on the wrapper the default PNDM path uses: nothing is launched"""
+    shape = (1, 4, 2, 4, 4)
+    x = torch.zeros(shape, device="cuda")
+    n = torch.zeros((2,) + shape[1:], device="cuda")
+    hist = torch.zeros((2,) + shape, device="cuda")
+    with pytest.raises(ValueError, match="contiguous"):
+        ops.guided_step(n, 2, 4.0, x, torch.zeros((1, 4, 2, 8, 4), device="cuda")[:, :, :, ::2], 0.9, -0.3)
+    with pytest.raises(ValueError, match="n_branch times"):
+        ops.guided_step(n[:1], 2, 4.0, x, x, 0.9, -0.3)
+    with pytest.raises(ValueError, match="slots"):
+        ops.guided_step(n, 2, 4.0, x, x, 0.9, -0.3, eps_hist=hist, store_slot=2)
+    with pytest.raises(ValueError, match="slots"):
+        ops.guided_step(n, 2, 4.0, x, x, 0.9, -0.3, eps_hist=None, hist_idx=(0,), w=(1.0,))
+    with pytest.raises(ValueError, match="slots"):
+        ops.guided_step(n, 2, 4.0, x, x, 0.9, -0.3, eps_hist=hist, hist_idx=(-1,), w=(1.0,))
+    assert not x.any() and not hist.any()
+
+
 def test_vae_postprocess(ops):
     n, H, W = 3, 16, 8
     rows = rnd(n * H * W, 4, seed=1)

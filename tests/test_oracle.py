@@ -7,6 +7,7 @@
    torch built-ins and closed-form known answers.
 """
 import math
+from types import SimpleNamespace
 
 import pytest
 import torch
@@ -184,8 +185,7 @@ def test_product_scheduler_matches_oracle(kind, steps, aliased):
     x_ref = torch.randn(shape, generator=g)
     x_obj = x_ref.clone()
     x_prod = x_ref.clone()
-    hist = torch.zeros((4,) + shape)
-    saved = torch.zeros(shape)
+    bufs = SimpleNamespace(_hist=torch.zeros((4,) + shape), _saved=torch.zeros(shape), _x_last=None)
     frame0 = x_ref[:, :, 0].clone()
     for i, t in enumerate(ref.timesteps):
         eps = torch.randn(shape, generator=g)
@@ -196,11 +196,7 @@ def test_product_scheduler_matches_oracle(kind, steps, aliased):
         else:
             x_ref = torch.cat([x_ref[:, :, :1], ref.step(eps[:, :, 1:], t, x_ref[:, :, 1:].clone())], 2)
             x_obj = torch.cat([x_obj[:, :, :1], obj.step(eps[:, :, 1:], t, x_obj[:, :, 1:].clone()).prev_sample], 2)
-        p = prod.plan_step(i)
-        if p.save_sample:
-            saved.copy_(x_prod)
-        emu_ops.guided_step(eps, 1, 1.0, saved if p.use_saved_sample else x_prod, x_prod, p.ca, p.cb, eps_hist=hist,
-                            store_slot=p.store_slot, w_cur=p.w_cur, hist_idx=p.hist_idx, w=p.hist_w)
+        prod.plan_step(i).launch(emu_ops, eps, 1, 1.0, 0.0, x_prod, bufs)      # what DenoiseEngine.step does with the plan
         assert rel_l2(x_obj, x_ref) < 1e-5, (i, int(t))
         assert rel_l2(x_prod, x_ref) < 1e-5, (i, int(t))
         assert torch.equal(x_prod[:, :, 0], frame0)

@@ -290,14 +290,14 @@ def test_tables_are_the_dpm_class_s():
 
 
 def test_step_table_writer_round_trips(tmp_path):
-    """plan.export_unipc_steps: the table tools/plan_host.cpp's denoise_unipc reads (88 bytes per step)"""
+    """plan.export_steps: the table tools/plan_host.cpp's denoise_unipc reads (88 bytes per step)"""
     from asva_amd import plan
 
     s = _sched(solver_order=3, disable_corrector=[2])
     s.set_timesteps(7)
     plans = [s.plan_step(i) for i in range(7)]
     path = tmp_path / "steps_unipc.bin"
-    plan.export_unipc_steps(str(path), s.timesteps.tolist(), plans)
+    plan.export_steps(str(path), s.timesteps.tolist(), plans)
     raw = path.read_bytes()
     assert len(raw) == 7 * 88
     f32 = lambda vs: np.array(vs, dtype=np.float32)  # noqa: E731

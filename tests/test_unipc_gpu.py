@@ -215,7 +215,7 @@ def test_sd15_clip_through_pipeline_unipc_10_steps():
 @pytest.mark.parametrize("graph", ["0", "1"])
 def test_cpp_host_runs_the_unipc_loop_without_python(tmp_path, graph):
     """test_dpmsolver_gpu.py::test_cpp_host_runs_the_dpmsolver_loop_without_python for UniPC-2, 10 steps: the table written by
-    plan.export_unipc_steps, plan_host's `denoise_unipc` — latents byte-identical to the Python engine's"""
+    plan.export_steps, plan_host's `denoise_unipc` — latents byte-identical to the Python engine's"""
     from asva_amd import _lib, build, plan
     from asva_amd.engine import DenoiseEngine
     from asva_amd.schedulers import UniPCMultistepScheduler
@@ -228,7 +228,7 @@ def test_cpp_host_runs_the_unipc_loop_without_python(tmp_path, graph):
     eng.set_conditioning(g["text"][:1].cuda(), g["audio"][1:2].cuda(), g["audio"][:1].cuda(), g["mask"], lat0.shape[2])
     want = eng.run(lat0, 10)
     torch.cuda.synchronize()
-    plan.export_unipc_steps(str(tmp_path / "steps_unipc.bin"), eng._ts.tolist(), eng._plans)
+    plan.export_steps(str(tmp_path / "steps_unipc.bin"), eng._ts.tolist(), eng._plans)
     for name, tns in (("text", r["text"]), ("audio", r["audio"]), ("latents", lat0)):
         _bytes(tns).cpu().numpy().tofile(str(tmp_path / f"{name}.in"))
     b, c, f, h, w = r["shape"]

@@ -96,15 +96,10 @@ def main():
         sched = PNDMScheduler() if a.scheduler == "pndm" else DDIMScheduler()
     eng = DenoiseEngine(unet, sched, audio_guidance_scale=4.0)
     eng.prepare(lat0, a.steps)
-    if a.scheduler == "dpmsolver++":
-        steps_file, denoise = "steps_ms.bin", "denoise_ms"
-        plan.export_multistep_steps(os.path.join(a.out, steps_file), eng._ts.tolist(), eng._plans)
-    elif a.scheduler == "unipc":
-        steps_file, denoise = "steps_unipc.bin", "denoise_unipc"
-        plan.export_unipc_steps(os.path.join(a.out, steps_file), eng._ts.tolist(), eng._plans)
-    else:
-        steps_file, denoise = "steps.bin", "denoise"
-        plan.export_steps(os.path.join(a.out, steps_file), eng._ts.tolist(), eng._plans)
+    # plan_host reads each plan type's table with a command of its own
+    steps_file, denoise = {"dpmsolver++": ("steps_ms.bin", "denoise_ms"), "unipc": ("steps_unipc.bin", "denoise_unipc")}.get(
+        a.scheduler, ("steps.bin", "denoise"))
+    plan.export_steps(os.path.join(a.out, steps_file), eng._ts.tolist(), eng._plans)
     for name, tns in (("text", text), ("audio", audio), ("latents", lat0)):
         _bytes(tns).cpu().numpy().tofile(os.path.join(a.out, name + ".in"))
     prog = [f"load text {a.out}/text.in", f"load audio {a.out}/audio.in", f"load latents {a.out}/latents.in", "run set_conditioning",

@@ -14,10 +14,10 @@
 //                                              PLAN_HOST_GRAPH=1: the forward plan is captured once into a hipGraph and
 //                                              replayed (avsd_plan_run only issues launches on the stream it is given)
 //   denoise_ms <steps_ms.bin> <latents> <x> <t> <noise> <n_branch> <g> <g2> <B> <C> <F> <HW>
-//                                              the same loop with a DPM-Solver++ table (asva_amd/plan.py:
-//                                              export_multistep_steps): the update is avsd_guided_multistep
+//                                              the same loop with a DPM-Solver++ table (schedulers.MultistepPlan.record):
+//                                              the update is avsd_guided_multistep
 //   denoise_unipc <steps_unipc.bin> <latents> <x> <t> <noise> <n_branch> <g> <g2> <B> <C> <F> <HW>
-//                                              the same loop with a UniPC table (asva_amd/plan.py: export_unipc_steps): the
+//                                              the same loop with a UniPC table (schedulers.UniPCPlan.record): the
 //                                              update is avsd_guided_unipc, corrector and predictor in one launch
 //   copy <src> <dst> <bytes>                   device-to-device between regions
 //   save <region> <file>                       download a region to a file
@@ -75,7 +75,7 @@ static void sym(void* h, const char* name, T& fn) {
   }
 }
 
-// one entry of the scheduler table (asva_amd/plan.py: export_steps; schedulers.StepPlan)
+// one entry of the scheduler table (asva_amd/plan.py: export_steps; schedulers.StepPlan.record)
 struct Step {
   float t, ca, cb, w_cur;
   int32_t store_slot, n_hist, save_sample, use_saved;
@@ -83,7 +83,7 @@ struct Step {
   float hist_w[4];
 };
 
-// one entry of the DPM-Solver++ table (asva_amd/plan.py: export_multistep_steps; schedulers.MultistepPlan)
+// one entry of the DPM-Solver++ table (asva_amd/plan.py: export_steps; schedulers.MultistepPlan.record)
 struct MsStep {
   float t, ca, c_cur, s_x, s_e;
   int32_t store_slot, n_hist;
@@ -91,7 +91,7 @@ struct MsStep {
   float hist_w[4];
 };
 
-// one entry of the UniPC table (asva_amd/plan.py: export_unipc_steps; schedulers.UniPCPlan)
+// one entry of the UniPC table (asva_amd/plan.py: export_steps; schedulers.UniPCPlan.record)
 struct UniPCStep {
   float t, s_x, s_e, cc_last, cc_cur, cp_x, cp_cur;
   int32_t use_corrector, store_slot, n_hist;
