@@ -74,6 +74,8 @@ const Entry kEntries[] = {
     AVSD_PLAN_ENTRY(avsd_groupnorm_fused),  AVSD_PLAN_ENTRY(avsd_groupnorm_fused_x2),
     AVSD_PLAN_ENTRY(avsd_ln_fold),          AVSD_PLAN_ENTRY(avsd_guided_multistep),      AVSD_PLAN_ENTRY(avsd_guided_unipc),
     AVSD_PLAN_ENTRY(avsd_window_turnover),
+    // random numbers (csrc/philox.h, csrc/rng.hip)
+    AVSD_PLAN_ENTRY(avsd_philox4x32_u32),   AVSD_PLAN_ENTRY(avsd_randn_philox_f32),
     // AVSync scorer (csrc/avsync.hip)
     AVSD_PLAN_ENTRY(avsd_convnd_f32),       AVSD_PLAN_ENTRY(avsd_maxpool_hw_f32),        AVSD_PLAN_ENTRY(avsd_mean_rows_f32),
     AVSD_PLAN_ENTRY(avsd_resize_aa_normalize_f32),

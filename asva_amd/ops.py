@@ -1411,6 +1411,42 @@ def guided_multistep(noise_pred: torch.Tensor, n_branch: int, g: float, x_in: to
           "avsd_guided_multistep")
 
 
+def _rng_ids(who: str, seed: int, stream: int, step: int):
+    seed, stream, step = int(seed), int(stream), int(step)
+    if not (0 <= seed < 1 << 64 and 0 <= stream < 1 << 32 and 0 <= step < 1 << 32):
+        raise ValueError(f"{who}: seed is 64 bits and stream / step are 32 bits, all unsigned (seed={seed} stream={stream} step={step})")
+    return seed, stream, step
+
+
+def _philox_fill(entry: str, dtype, n: int, seed: int, stream: int, step: int, first: int, device, out) -> torch.Tensor:
+    n, first = int(n), int(first)
+    seed, stream, step = _rng_ids(entry, seed, stream, step)
+    if n < 0 or first < 0 or first + n >= 1 << 63:
+        raise ValueError(f"{entry}: need n >= 0 and 0 <= first, first + n < 2^63 (n={n} first={first})")
+    if out is None:
+        out = torch.empty(n, dtype=dtype, device=device)
+    _req(out, dtype, "out")
+    if not out.is_contiguous() or out.numel() != n:
+        raise ValueError(f"{entry}: out must be contiguous with {n} elements")
+    if n:
+        check(getattr(_lib.lib(), entry)(_p(out), n, seed, stream, step, first, _stream()), entry)
+    return out
+
+
+def philox_u32(n_words: int, seed: int, stream: int = 0, step: int = 0, first_word: int = 0, device="cuda",
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """avsd_philox4x32_u32 (include/avsd.h): words first_word .. first_word + n_words - 1 of the Philox4x32-10 sequence, as int32
+    bit patterns (torch has no uint32 arithmetic; view the result as numpy uint32)."""
+    return _philox_fill("avsd_philox4x32_u32", torch.int32, n_words, seed, stream, step, first_word, device, out)
+
+
+def randn_philox(n: int, seed: int, stream: int = 0, step: int = 0, first: int = 0, device="cuda",
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """avsd_randn_philox_f32 (include/avsd.h): normals first .. first + n - 1 of the sequence (seed, stream, step), f32, flat; `out`
+    (any shape, contiguous, n elements) is filled in place when given."""
+    return _philox_fill("avsd_randn_philox_f32", F32, n, seed, stream, step, first, device, out)
+
+
 def guided_unipc(noise_pred: torch.Tensor, n_branch: int, g: float, x_in: torch.Tensor, x_out: torch.Tensor, x_last: torch.Tensor,
                  use_corrector: bool, s_x: float, s_e: float, cc_last: float, cc_cur: float, cp_x: float, cp_cur: float, *,
                  hist: Optional[torch.Tensor] = None, store_slot: int = -1, hist_idx=(), wc=(), wp=(), g2: float = 0.0) -> None:

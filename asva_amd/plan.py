@@ -77,6 +77,8 @@ class _Proxy:
                 out.append(("S",) if k == last else ("p", 0 if a is None else int(a)))
             elif tp in (C.c_int, C.c_int64, C.c_int32):
                 out.append(("i", int(a)))
+            elif tp in (C.c_uint32, C.c_uint64):              # seeds and stream ids: 'i' holds the same 64 bits, signed
+                out.append(("i", int(a) - (1 << 64) if int(a) >= 1 << 63 else int(a)))
             elif tp is C.c_float:
                 out.append(("f", float(a)))
             elif isinstance(tp, type) and issubclass(tp, C._Pointer):

@@ -411,6 +411,20 @@ int avsd_guided_multistep(const float* noise_pred, int n_branch, float g, float 
                           float* x_out, float ca, float c_cur, float s_x, float s_e, int B, int C, int F,
                           int HW, void* stream);
 
+/* ---- random numbers (csrc/philox.h, csrc/rng.hip): integers and f32 in both builds ----
+ * Philox4x32-10 as published by Random123 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85, ten
+ * rounds) with key = (seed lo, seed hi) and counter = (block lo, block hi, step, stream).  Item j of a sequence is lane j & 3 of
+ * block j >> 2 (64-bit), so every item is a pure function of (seed, stream, step, j): a range may be produced in any partition,
+ * with the same bits.
+ *   avsd_philox4x32_u32:   out[k] = word first_word + k, 0 <= k < n_words
+ *   avsd_randn_philox_f32: out[k] = normal first + k, 0 <= k < n.  Box-Muller in f32: with w0..w3 the words of a block,
+ *       u = ((w0 >> 9) + 0.5) 2^-23 in (0, 1), v = (w1 >> 8) 2^-24 in [0, 1), r = sqrtf(-2 logf(u)),
+ *       lane 0 = r cos(2 pi v), lane 1 = r sin(2 pi v) (sincospif(2v)); lanes 2 and 3 the same from w2, w3.  |z| <= 5.77.
+ * first / first_word and the counts need not be multiples of 4; out needs 4-byte alignment.  A count of 0 launches nothing. */
+int avsd_philox4x32_u32(uint32_t* out, int64_t n_words, uint64_t seed, uint32_t stream, uint32_t step, int64_t first_word,
+                        void* hip_stream);
+int avsd_randn_philox_f32(float* out, int64_t n, uint64_t seed, uint32_t stream, uint32_t step, int64_t first, void* hip_stream);
+
 /* Guidance + UniPC step (corrector, then predictor) on (B, C, F, H, W) f32 latents, frame 0 pinned, one launch:
  *   eps  = guidance combine of noise_pred (n_branch 1 / 2 / 3, g, g2: exactly the rule of avsd_guided_step)
  *   d    = s_x * x_in + s_e * eps            (data prediction m_i of the PREDICTED sample x_in the UNet just saw)
