@@ -844,13 +844,20 @@ def gemm_f32(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = No
 
 
 def gemm_batched(a: torch.Tensor, w: torch.Tensor, *, alpha: float = 1.0, out_f32: bool = False,
-                 bias: Optional[torch.Tensor] = None, tile: int = 0, ln: Optional[tuple] = None) -> torch.Tensor:
-    """out[b] = alpha * a[b] . w[b]^T for 3-D a [B, M, K], w [B, N, K] (VAE mid-block attention)."""
+                 bias: Optional[torch.Tensor] = None, tile: int = 0, ln: Optional[tuple] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[b] = alpha * a[b] . w[b]^T for 3-D a [B, M, K], w [B, N, K] (VAE mid-block attention).  `out`: [B, M, N] of the output type, rows
+    contiguous (any row and batch stride the descriptor's alignment rules admit)."""
     _req(a, P.ACT, "a")
     _req(w, P.ACT, "w")
     B, M, K = a.shape
     N = w.shape[1]
-    out = torch.empty((B, M, N), dtype=F32, device=a.device) if out_f32 else alloc16((B, M, N), a.device)
+    if out is None:
+        out = torch.empty((B, M, N), dtype=F32, device=a.device) if out_f32 else alloc16((B, M, N), a.device)
+    else:
+        _req(out, F32 if out_f32 else P.ACT, "out")
+        if tuple(out.shape) != (B, M, N):
+            raise ValueError(f"gemm_batched: out must be [{B}, {M}, {N}], got {tuple(out.shape)}")
     d = GemmDesc()
     d.A, d.W, d.out = _p(a), _p(w), _p(out)
     d.M, d.N, d.K, d.k_split = M, N, K, K
