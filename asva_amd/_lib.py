@@ -113,6 +113,12 @@ SIGNATURES = {
                                       c_int, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int, c_int, c_int, c_int, c_void_p]),
     "avsd_philox4x32_u32": (c_int, [c_void_p, c_int64, C.c_uint64, C.c_uint32, C.c_uint32, c_int64, c_void_p]),
     "avsd_randn_philox_f32": (c_int, [c_void_p, c_int64, C.c_uint64, C.c_uint32, C.c_uint32, c_int64, c_void_p]),
+    "avsd_guided_step_sde": (c_int, [c_void_p, c_int, c_float, c_float, c_void_p, c_int, c_float, C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                     c_int, c_void_p, c_void_p, c_float, c_float, c_int, c_int, c_int, c_int, c_float, C.c_uint64,
+                                     C.c_uint32, C.c_uint32, c_void_p]),
+    "avsd_guided_multistep_sde": (c_int, [c_void_p, c_int, c_float, c_float, c_void_p, c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                          c_int, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int, c_int, c_int, c_int,
+                                          c_float, C.c_uint64, C.c_uint32, C.c_uint32, c_void_p]),
     "avsd_guided_unipc": (c_int, [c_void_p, c_int, c_float, c_float, c_void_p, c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float),
                                   C.POINTER(C.c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float,
                                   c_float, c_float, c_int, c_int, c_int, c_int, c_void_p]),

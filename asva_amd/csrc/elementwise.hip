@@ -8,6 +8,7 @@
 // frames 1..), :206-213 (decode post-processing).  diffusers 0.29.2 get_timestep_embedding /
 // PNDMScheduler.step_plms / DDIMScheduler.step supply the formulas.
 #include "avsd_common.h"
+#include "philox.h"
 
 namespace {
 
@@ -180,6 +181,138 @@ __global__ void guided_multistep_kernel(const MultistepArgs a) {
   }
 }
 
+// ---- the stochastic forms of the two kernels above (DDIM eta > 0, SDE-DPM-Solver++; include/avsd.h): the same update plus
+// c_noise z, the normal z evaluated in registers (csrc/philox.h).  V = 4: a thread owns four consecutive elements of one frame row
+// and moves them as float4 (HW % 4 == 0, every base pointer 16-byte aligned: the entry point decides); V = 1: one element per
+// thread.  Every element goes through the same scalar expressions in both, so the two paths give the same bits.
+struct NoiseArgs {
+  float c_noise;
+  philox::Key key;   // key.stream is the stream of batch row 0: row b draws from stream + b
+};
+
+template <int V>
+__device__ __forceinline__ void ldv(const float* p, float (&v)[V]) {
+  if constexpr (V == 4) {
+    const float4 t = *reinterpret_cast<const float4*>(p);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+    v[0] = *p;
+  }
+}
+
+template <int V>
+__device__ __forceinline__ void stv(float* p, const float (&v)[V]) {
+  if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  else *p = v[0];
+}
+
+// guided_eps for V consecutive elements
+template <int V>
+__device__ __forceinline__ void guided_eps_v(const StepArgs& s, int64_t per, int64_t i, float (&eps)[V]) {
+  ldv<V>(s.noise_pred + i, eps);
+  if (s.n_branch >= 2) {
+    float e1[V], e2[V];
+    ldv<V>(s.noise_pred + per + i, e1);
+    if (s.n_branch == 3) ldv<V>(s.noise_pred + 2 * per + i, e2);
+#pragma unroll
+    for (int l = 0; l < V; ++l) {
+      float gsum = eps[l] + s.g * (e1[l] - eps[l]);
+      if (s.n_branch == 3) gsum = gsum + s.g2 * (e2[l] - e1[l]);
+      eps[l] = gsum;
+    }
+  }
+}
+
+// history entry k for V consecutive elements: the freshly stored slot is read back from the register copy
+template <int V>
+__device__ __forceinline__ void hist_v(const StepArgs& s, int64_t per, int64_t i, int k, const float (&cur)[V], float (&h)[V]) {
+  if (s.hist_idx[k] == s.store_slot) {
+#pragma unroll
+    for (int l = 0; l < V; ++l) h[l] = cur[l];
+  } else {
+    ldv<V>(s.hist + (int64_t)s.hist_idx[k] * per + i, h);
+  }
+}
+
+// x_out[i .. i + V) = acc + c_noise z on frames 1.., x_in on frame 0.  Element (b, c, f >= 1, p) takes normal
+// j = (c (F - 1) + (f - 1)) HW + p of (seed, stream + b, step): lane j & 3 of block j >> 2.  With V = 4, i and HW are multiples of
+// 4, so j is one too and the four elements are the four lanes of one block.
+template <int V>
+__device__ __forceinline__ void store_noisy(const StepArgs& s, const NoiseArgs& nz, int64_t i, const float (&xin)[V],
+                                            const float (&acc)[V]) {
+  const int64_t fhw = (int64_t)s.F * s.HW;
+  const int64_t bc = i / fhw, q = i - bc * fhw;    // bc = b C + c,  q = f HW + p
+  if (q < s.HW) {                                   // frame 0: copied through, no normal spent
+    stv<V>(s.x_out + i, xin);
+    return;
+  }
+  const uint32_t b = (uint32_t)bc / (uint32_t)s.C, c = (uint32_t)bc - b * (uint32_t)s.C;     // B C < 2^31 (noise_require)
+  const uint64_t j = (uint64_t)c * (uint64_t)(fhw - s.HW) + (uint64_t)(q - s.HW);
+  philox::Key key = nz.key;
+  key.stream += b;
+  // an empty statement that only makes the key opaque here: the ten round keys are then derived inside the loop body instead of
+  // being kept live across it in 20 scalar registers, which the float4 kernels do not have to spare.  Register allocation only:
+  // without it the results are the same bits and asva_amd/resource_usage_gfx950.json shows two scalar spills in one kernel.
+  asm volatile("" : "+s"(key.k0), "+s"(key.k1));
+  float z[4], out[V];
+  philox::normal4(key, j >> 2, z);
+  if constexpr (V == 4) {
+#pragma unroll
+    for (int l = 0; l < 4; ++l) out[l] = fmaf(nz.c_noise, z[l], acc[l]);
+  } else {
+    const int lane = (int)(j & 3);
+    const float zl = lane == 0 ? z[0] : lane == 1 ? z[1] : lane == 2 ? z[2] : z[3];
+    out[0] = fmaf(nz.c_noise, zl, acc[0]);
+  }
+  stv<V>(s.x_out + i, out);
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void guided_step_sde_kernel(const GuidedArgs a, const NoiseArgs nz) {
+  const StepArgs& s = a.s;
+  const int64_t per = (int64_t)s.B * s.C * s.F * s.HW;
+  for (int64_t i = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) * V; i < per; i += (int64_t)gridDim.x * blockDim.x * V) {
+    float eps[V], e[V], xin[V], acc[V];
+    guided_eps_v<V>(s, per, i, eps);
+    if (s.hist && s.store_slot >= 0) stv<V>(s.hist + (int64_t)s.store_slot * per + i, eps);
+#pragma unroll
+    for (int l = 0; l < V; ++l) e[l] = a.w_cur * eps[l];
+    for (int k = 0; k < s.n_hist; ++k) {
+      float h[V];
+      hist_v<V>(s, per, i, k, eps, h);
+#pragma unroll
+      for (int l = 0; l < V; ++l) e[l] = fmaf(a.w[k], h[l], e[l]);
+    }
+    ldv<V>(s.x_in + i, xin);
+#pragma unroll
+    for (int l = 0; l < V; ++l) acc[l] = fmaf(a.ca, xin[l], a.cb * e[l]);
+    store_noisy<V>(s, nz, i, xin, acc);
+  }
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void guided_multistep_sde_kernel(const MultistepArgs a, const NoiseArgs nz) {
+  const StepArgs& s = a.s;
+  const int64_t per = (int64_t)s.B * s.C * s.F * s.HW;
+  for (int64_t i = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) * V; i < per; i += (int64_t)gridDim.x * blockDim.x * V) {
+    float eps[V], xin[V], d[V], acc[V];
+    guided_eps_v<V>(s, per, i, eps);
+    ldv<V>(s.x_in + i, xin);
+#pragma unroll
+    for (int l = 0; l < V; ++l) d[l] = fmaf(a.s_x, xin[l], a.s_e * eps[l]);
+    if (s.hist && s.store_slot >= 0) stv<V>(s.hist + (int64_t)s.store_slot * per + i, d);
+#pragma unroll
+    for (int l = 0; l < V; ++l) acc[l] = fmaf(a.c_cur, d[l], a.ca * xin[l]);
+    for (int k = 0; k < s.n_hist; ++k) {
+      float h[V];
+      hist_v<V>(s, per, i, k, d, h);
+#pragma unroll
+      for (int l = 0; l < V; ++l) acc[l] = fmaf(a.w[k], h[l], acc[l]);
+    }
+    store_noisy<V>(s, nz, i, xin, acc);
+  }
+}
+
 struct UniPCArgs {
   StepArgs s;
   float* x_last;
@@ -345,6 +478,21 @@ inline void pad4(float* dst, const float* src, int n) {
   for (int k = 0; k < 4; ++k) dst[k] = k < n ? src[k] : 0.f;
 }
 
+// What the two avsd_guided_*_sde entry points add to step_require: batch row b draws from stream + b, which must stay a 32-bit id,
+// and the kernels split b C + c with a 32-bit division.
+int noise_require(const char* who, NoiseArgs& nz, float c_noise, uint64_t seed, uint32_t stream, uint32_t step, int B, int C) {
+  AVSD_REQUIRE((uint64_t)stream + (uint64_t)B <= (1ull << 32), "%s: stream + B exceeds 2^32 (stream=%u B=%d)", who, stream, B);
+  AVSD_REQUIRE((int64_t)B * C <= INT32_MAX, "%s: B * C exceeds 2^31 - 1 (B=%d C=%d)", who, B, C);
+  nz = NoiseArgs{c_noise, philox::make_key(seed, stream, step)};
+  return AVSD_OK;
+}
+
+// the float4 path: whole frame rows of 4-element groups, and every pointer the kernel offsets by multiples of 16 bytes aligned
+inline bool step_vectorizes(const StepArgs& s) {
+  const uintptr_t bits = (uintptr_t)s.noise_pred | (uintptr_t)s.x_in | (uintptr_t)s.x_out | (uintptr_t)s.hist;
+  return s.HW % 4 == 0 && bits % 16 == 0;
+}
+
 }  // namespace
 
 extern "C" int avsd_ncfhw_to_rows_x2(const float* src, void* dst, int64_t dst_lo, int B, int C, int F, int HW, int cpad, int rep,
@@ -435,6 +583,51 @@ extern "C" int avsd_guided_multistep(const float* noise_pred, int n_branch, floa
   const int64_t n = (int64_t)B * C * F * HW;
   hipLaunchKernelGGL(guided_multistep_kernel, dim3(grid_for(n, 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
   AVSD_CHECK_LAUNCH("guided_multistep launch");
+  return AVSD_OK;
+}
+
+extern "C" int avsd_guided_step_sde(const float* noise_pred, int n_branch, float g, float g2, float* eps_hist, int store_slot,
+                                    float w_cur, const int32_t* hist_idx, const float* w, int n_hist, const float* x_in,
+                                    float* x_out, float ca, float cb, int B, int C, int F, int HW, float c_noise, uint64_t seed,
+                                    uint32_t stream, uint32_t step, void* hip_stream) {
+  GuidedArgs a;
+  NoiseArgs nz;
+  if (int rc = step_require("guided_step_sde", a.s, noise_pred, n_branch, g, g2, eps_hist, store_slot, hist_idx, w != nullptr, n_hist,
+                            x_in, x_out, B, C, F, HW))
+    return rc;
+  if (int rc = noise_require("guided_step_sde", nz, c_noise, seed, stream, step, B, C)) return rc;
+  pad4(a.w, w, n_hist);
+  a.w_cur = w_cur; a.ca = ca; a.cb = cb;
+  const int64_t n = (int64_t)B * C * F * HW;
+  if (step_vectorizes(a.s))
+    hipLaunchKernelGGL(guided_step_sde_kernel<4>, dim3(grid_for(n / 4, 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream), a,
+                       nz);
+  else
+    hipLaunchKernelGGL(guided_step_sde_kernel<1>, dim3(grid_for(n, 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream), a, nz);
+  AVSD_CHECK_LAUNCH("guided_step_sde launch");
+  return AVSD_OK;
+}
+
+extern "C" int avsd_guided_multistep_sde(const float* noise_pred, int n_branch, float g, float g2, float* hist, int store_slot,
+                                         const int32_t* hist_idx, const float* w, int n_hist, const float* x_in, float* x_out,
+                                         float ca, float c_cur, float s_x, float s_e, int B, int C, int F, int HW, float c_noise,
+                                         uint64_t seed, uint32_t stream, uint32_t step, void* hip_stream) {
+  MultistepArgs a;
+  NoiseArgs nz;
+  if (int rc = step_require("guided_multistep_sde", a.s, noise_pred, n_branch, g, g2, hist, store_slot, hist_idx, w != nullptr, n_hist,
+                            x_in, x_out, B, C, F, HW))
+    return rc;
+  if (int rc = noise_require("guided_multistep_sde", nz, c_noise, seed, stream, step, B, C)) return rc;
+  pad4(a.w, w, n_hist);
+  a.ca = ca; a.c_cur = c_cur; a.s_x = s_x; a.s_e = s_e;
+  const int64_t n = (int64_t)B * C * F * HW;
+  if (step_vectorizes(a.s))
+    hipLaunchKernelGGL(guided_multistep_sde_kernel<4>, dim3(grid_for(n / 4, 256)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(hip_stream), a, nz);
+  else
+    hipLaunchKernelGGL(guided_multistep_sde_kernel<1>, dim3(grid_for(n, 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream),
+                       a, nz);
+  AVSD_CHECK_LAUNCH("guided_multistep_sde launch");
   return AVSD_OK;
 }
 

@@ -76,6 +76,8 @@ const Entry kEntries[] = {
     AVSD_PLAN_ENTRY(avsd_window_turnover),
     // random numbers (csrc/philox.h, csrc/rng.hip)
     AVSD_PLAN_ENTRY(avsd_philox4x32_u32),   AVSD_PLAN_ENTRY(avsd_randn_philox_f32),
+    // stochastic scheduler steps (csrc/elementwise.hip): the 64-bit seed travels in the 'i' tag's 64 bits, as above
+    AVSD_PLAN_ENTRY(avsd_guided_step_sde),  AVSD_PLAN_ENTRY(avsd_guided_multistep_sde),
     // AVSync scorer (csrc/avsync.hip)
     AVSD_PLAN_ENTRY(avsd_convnd_f32),       AVSD_PLAN_ENTRY(avsd_maxpool_hw_f32),        AVSD_PLAN_ENTRY(avsd_mean_rows_f32),
     AVSD_PLAN_ENTRY(avsd_resize_aa_normalize_f32),
@@ -309,6 +311,8 @@ static int plan_bundle_load_impl(const char* path, avsd_plan_bundle** out) {
             return fail("avsd_guided_step history tables are 4 entries of 4 bytes");   // the entry point reads up to n_hist <= 4
           } else if (c.fn == "avsd_guided_multistep" && n != 0 && n != 16) {
             return fail("avsd_guided_multistep history tables are 4 entries of 4 bytes");
+          } else if ((c.fn == "avsd_guided_step_sde" || c.fn == "avsd_guided_multistep_sde") && n != 0 && n != 16) {
+            return fail("avsd_guided_*_sde history tables are 4 entries of 4 bytes");
           } else if (c.fn == "avsd_guided_unipc" && n != 0 && n != 16) {
             return fail("avsd_guided_unipc history tables are 4 entries of 4 bytes");
           }

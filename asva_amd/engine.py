@@ -99,11 +99,23 @@ class DenoiseEngine:
         self._graph.replay()
         return self._noise_static
 
-    def prepare(self, latents: torch.Tensor, num_inference_steps: int):
+    def prepare(self, latents: torch.Tensor, num_inference_steps: int, generator=None):
+        """`generator`: the DeviceGenerator of a stochastic sampler's noise (DDIM eta > 0, SDE-DPM-Solver++).  Each call takes one
+        fresh stream per batch row from it; step i of row b then evaluates the normals (seed, stream0 + b, i) inside its launch
+        (schedulers.NoisyStepPlan / NoisyMultistepPlan).  Deterministic samplers take none and leave it untouched."""
         dev = latents.device
         self.scheduler.set_timesteps(num_inference_steps, device=dev)
+        plans = [self.scheduler.plan_step(i) for i in range(self.scheduler.num_forwards())]
+        self._noise_key = None
+        if any(getattr(p, "noisy", False) for p in plans):
+            from .rng import DeviceGenerator
+
+            if not isinstance(generator, DeviceGenerator):
+                raise ValueError(f"{type(self.scheduler).__name__} is stochastic here: prepare() / run() need generator=DeviceGenerator(seed), "
+                                 f"got {type(generator).__name__}")
+            self._noise_key = (generator.seed, generator.take_streams(latents.shape[0]))
         self._ts = self.scheduler.timesteps.to(dev, torch.float32)
-        self._plans = [self.scheduler.plan_step(i) for i in range(self.scheduler.num_forwards())]
+        self._plans = plans
         self._hist = torch.zeros((4,) + tuple(latents.shape), dtype=torch.float32, device=dev)
         self._saved = torch.empty_like(latents)
         self._x_last = torch.zeros_like(latents)       # UniPC: the corrected sample, base of the next step's corrector
@@ -115,9 +127,9 @@ class DenoiseEngine:
         self._plans[i].launch(ops, noise, self.n_branch, self.g, self.g2, latents, self)
 
     @torch.no_grad()
-    def run(self, latents: torch.Tensor, num_inference_steps: int) -> torch.Tensor:
+    def run(self, latents: torch.Tensor, num_inference_steps: int, generator=None) -> torch.Tensor:
         latents = latents.to(torch.float32).contiguous().clone()
-        self.prepare(latents, num_inference_steps)
+        self.prepare(latents, num_inference_steps, generator)
         for i in range(len(self._plans)):
             self.step(latents, i)
         return latents

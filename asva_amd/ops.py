@@ -1425,6 +1425,42 @@ def _rng_ids(who: str, seed: int, stream: int, step: int):
     return seed, stream, step
 
 
+def _noise_key(who: str, B: int, c_noise: float, seed: int, stream: int, step: int):
+    """the trailing arguments of the two stochastic steps: batch row b draws from stream + b, which must stay a 32-bit id"""
+    seed, stream, step = _rng_ids(who, seed, stream, step)
+    if stream + B > 1 << 32:
+        raise ValueError(f"{who}: stream + B exceeds 2^32 (stream={stream} B={B})")
+    return float(c_noise), seed, stream, step
+
+
+def guided_step_sde(noise_pred: torch.Tensor, n_branch: int, g: float, x_in: torch.Tensor, x_out: torch.Tensor,
+                    ca: float, cb: float, *, eps_hist: Optional[torch.Tensor] = None, store_slot: int = -1,
+                    w_cur: float = 1.0, hist_idx=(), w=(), g2: float = 0.0, c_noise: float = 0.0, seed: int = 0, stream: int = 0,
+                    step: int = 0) -> None:
+    """avsd_guided_step_sde (include/avsd.h): guided_step plus c_noise * z on frames 1.., z the normals of (seed, stream + b, step)
+    in the layout (C, F - 1, H, W), evaluated inside the kernel."""
+    (B, Cc, Fr, HW), nh, idx, (ws,) = _step_args("guided_step_sde", noise_pred, n_branch, (x_in, x_out), eps_hist, store_slot, hist_idx,
+                                                 w=w)
+    key = _noise_key("guided_step_sde", B, c_noise, seed, stream, step)
+    check(_lib.lib().avsd_guided_step_sde(_p(noise_pred), n_branch, float(g), float(g2), _p(eps_hist), store_slot, float(w_cur), idx,
+                                          ws, nh, _p(x_in), _p(x_out), float(ca), float(cb), B, Cc, Fr, HW, *key, _stream()),
+          "avsd_guided_step_sde")
+
+
+def guided_multistep_sde(noise_pred: torch.Tensor, n_branch: int, g: float, x_in: torch.Tensor, x_out: torch.Tensor,
+                         ca: float, c_cur: float, s_x: float, s_e: float, *, hist: Optional[torch.Tensor] = None,
+                         store_slot: int = -1, hist_idx=(), w=(), g2: float = 0.0, c_noise: float = 0.0, seed: int = 0,
+                         stream: int = 0, step: int = 0) -> None:
+    """avsd_guided_multistep_sde (include/avsd.h): guided_multistep plus c_noise * z on frames 1.., z as in guided_step_sde."""
+    (B, Cc, Fr, HW), nh, idx, (ws,) = _step_args("guided_multistep_sde", noise_pred, n_branch, (x_in, x_out), hist, store_slot,
+                                                 hist_idx, w=w)
+    key = _noise_key("guided_multistep_sde", B, c_noise, seed, stream, step)
+    check(_lib.lib().avsd_guided_multistep_sde(_p(noise_pred), n_branch, float(g), float(g2), _p(hist), store_slot, idx, ws, nh,
+                                               _p(x_in), _p(x_out), float(ca), float(c_cur), float(s_x), float(s_e), B, Cc, Fr, HW,
+                                               *key, _stream()),
+          "avsd_guided_multistep_sde")
+
+
 def _philox_fill(entry: str, dtype, n: int, seed: int, stream: int, step: int, first: int, device, out) -> torch.Tensor:
     n, first = int(n), int(first)
     seed, stream, step = _rng_ids(entry, seed, stream, step)

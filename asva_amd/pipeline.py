@@ -168,11 +168,35 @@ class AudioCondAnimationPipeline:
         b = len(image_latents)
         shape = (b, num_channels_latents, video_length - 1, height // self.vae_scale_factor, width // self.vae_scale_factor)
         if noise is None:
-            noise = torch.randn(shape, generator=generator, device=device, dtype=dtype)
+            noise = self._randn(shape, generator, device, dtype)
         noise = noise.to(device=device, dtype=dtype)
         assert tuple(noise.shape) == shape, (noise.shape, shape)
         lat = torch.cat([image_latents.unsqueeze(2).to(device=device, dtype=dtype), noise], dim=2)
         return lat * self.scheduler.init_noise_sigma
+
+    @staticmethod
+    def _randn(shape, generator, device, dtype):
+        """initial noise: torch.randn, or with a DeviceGenerator one fresh stream per batch row"""
+        from .rng import DeviceGenerator
+
+        if isinstance(generator, DeviceGenerator):
+            return torch.stack([generator.normal(tuple(shape[1:]), device=device) for _ in range(shape[0])]).to(dtype)
+        return torch.randn(shape, generator=generator, device=device, dtype=dtype)
+
+    def _step_generator(self, generator, eta: float):
+        """`eta`, when given, reaches a scheduler that has one (DDIMScheduler.set_eta) and stays set; None leaves the scheduler's own
+        eta as it is.  For a stochastic scheduler (DDIM eta > 0,
+        SDE-DPM-Solver++) -> the DeviceGenerator of the steps' noise: `generator` itself when it is one; otherwise a new one
+        seeded by ONE torch.randint draw from `generator` (or torch's default one), made after the initial noise, so that a seeded
+        call stays reproducible.  Any other scheduler -> `generator` unchanged."""
+        from .rng import DeviceGenerator
+
+        if eta is not None and hasattr(self.scheduler, "set_eta"):
+            self.scheduler.set_eta(eta)
+        if not getattr(self.scheduler, "stochastic", False) or isinstance(generator, DeviceGenerator):
+            return generator
+        dev = generator.device if generator is not None else "cpu"
+        return DeviceGenerator(int(torch.randint(0, 2 ** 63 - 1, (1,), generator=generator, device=dev).item()))
 
     # -- __call__ (reference :263-375) ---------------------------------------------------------------------------------
     @torch.no_grad()
@@ -180,7 +204,7 @@ class AudioCondAnimationPipeline:
                  width: int = 256, num_inference_steps: int = 20, audio_guidance_scale: float = 4.0,
                  text_guidance_scale: float = 1.0, generator=None, return_dict: bool = True, *, image_latents=None,
                  audio_encodings=None, null_audio_encodings=None, audio_masks=None, noise=None, output_latents: bool = False,
-                 output_type: str = "float"):
+                 output_type: str = "float", eta: Optional[float] = None):
         device = self.device
         f32 = torch.float32
         do_text = text_guidance_scale > 1.0
@@ -197,17 +221,18 @@ class AudioCondAnimationPipeline:
         image_latents = image_latents.to(device=device, dtype=f32)
         latents = self.prepare_video_latents(image_latents, self.unet.config.in_channels, video_length, height, width, device,
                                              f32, generator, noise)                                      # (b, 4, f, h, w)
+        step_gen = self._step_generator(generator, eta)
 
         if self.use_engine and self._scheduler_plans():
             eng = self._engine_for(audio_guidance_scale, text_guidance_scale)
             self.unet.set_conditioning(text, audio, masks, video_length)      # already in the CFG branch order of :150-155,:186-194
-            eng.prepare(latents, num_inference_steps)
+            eng.prepare(latents, num_inference_steps, step_gen)
             latents = latents.contiguous().clone()
             for i in self.progress_bar(range(self.scheduler.num_forwards())):
                 eng.step(latents, i)
         else:
             latents = self._reference_style_loop(latents, text, audio, masks, video_length, num_inference_steps, do_text,
-                                                 do_audio, audio_guidance_scale, text_guidance_scale)
+                                                 do_audio, audio_guidance_scale, text_guidance_scale, eta, step_gen)
         if output_latents:
             return latents
         if output_type in ("uint8", "uint8_device"):     # (b, f, H, W, 3) uint8 frames, converted on the device
@@ -244,10 +269,12 @@ class AudioCondAnimationPipeline:
                       video_length: int = 12, height: int = 256, width: int = 256, num_inference_steps: int = 20,
                       audio_guidance_scale: float = 4.0, text_guidance_scale: float = 1.0, generator=None, handover: str = "latent",
                       output_type: str = "uint8", on_window: Optional[Callable] = None, sample_rate: int = 16000,
-                      audio_encodings=None, null_audio_encodings=None, audio_masks=None, n_samples: Optional[int] = None):
+                      audio_encodings=None, null_audio_encodings=None, audio_masks=None, n_samples: Optional[int] = None,
+                      eta: Optional[float] = None):
         """Animates ONE still over a whole audio track: W chained windows of `video_length` = F frames (data_utils.track_windows).
         Window 0 is `__call__` for one clip.  Window k > 0 starts from the last frame of window k-1, draws its F-1 noise frames from
-        the same `generator` (not re-seeded) and hears the audio that starts at its first frame's own time.
+        the same `generator` (not re-seeded) and hears the audio that starts at its first frame's own time.  With a stochastic
+        sampler (`eta` > 0 on DDIM, SDE-DPM-Solver++) every window's steps take fresh streams of one DeviceGenerator (`_step_generator`).
 
         handover  "latent": frame 0 of window k is the finished latent of frame F-1 of window k-1, bit for bit (no VAE round trip);
                   "pixel": that frame's decoded uint8 pixels are encoded again (`pixel_handover_latents`).
@@ -324,13 +351,14 @@ class AudioCondAnimationPipeline:
             if k == 0:                                                           # exactly the start of __call__ for one clip
                 x = self.prepare_video_latents(image_latents, self.unet.config.in_channels, F, height, width, device, f32,
                                                generator).contiguous().clone()
+                step_gen = self._step_generator(generator, eta)                  # one generator: every window takes fresh streams
             else:
-                noise = torch.randn((1, x.shape[1], F - 1) + tuple(x.shape[3:]), generator=generator, device=device, dtype=f32)
+                noise = self._randn((1, x.shape[1], F - 1) + tuple(x.shape[3:]), generator, device, f32)
                 ops.window_turnover(x, noise, x, sigma)                          # frame F-1 -> frame 0, fresh noise behind it
                 if handover == "pixel":
                     x[:, :, 0] = self.pixel_handover_latents(frames[F - 1]) * sigma
             self.unet.set_conditioning(text, cond[k], masks, F)                  # same shapes: refreshed in place, the graph stays
-            eng.prepare(x, num_inference_steps)
+            eng.prepare(x, num_inference_steps, step_gen)
             mark(k, "denoise")
             for i in self.progress_bar(range(self.scheduler.num_forwards())):
                 eng.step(x, i)
@@ -346,9 +374,17 @@ class AudioCondAnimationPipeline:
                 on_window(k, piece)
         return torch.cat(out)
 
-    def _reference_style_loop(self, latents, text, audio, masks, video_length, steps, do_text, do_audio, ag, tg):
+    def _reference_style_loop(self, latents, text, audio, masks, video_length, steps, do_text, do_audio, ag, tg, eta=None,
+                              generator=None):
         """The loop exactly as the reference writes it (:325-365): torch.cat duplication, unet(...).sample,
-        guidance in torch, scheduler.step on frames 1.. — any scheduler object, any guidance mix."""
+        guidance in torch, scheduler.step on frames 1.. — any scheduler object, any guidance mix.  `eta` and `generator` go to
+        `scheduler.step` only when its signature names them (the reference's prepare_extra_step_kwargs, :215-231)."""
+        import inspect
+
+        accepted = set(inspect.signature(self.scheduler.step).parameters)
+        if eta is None:                          # not chosen for this call: the scheduler's own (DDIMScheduler.set_eta), else none
+            eta = getattr(self.scheduler, "eta", 0.0)
+        extra = {k: v for k, v in (("eta", eta), ("generator", generator)) if k in accepted}
         self.scheduler.set_timesteps(steps, device=latents.device)
         k = 1 + int(do_text) + int(do_audio)
         txt = text[:, None].expand(-1, video_length, -1, -1)
@@ -368,7 +404,7 @@ class AudioCondAnimationPipeline:
             elif do_audio:
                 nt, nta = n.chunk(2)
                 n = nt + ag * (nta - nt)
-            latents[:, :, 1:] = self.scheduler.step(n[:, :, 1:], t, latents[:, :, 1:]).prev_sample
+            latents[:, :, 1:] = self.scheduler.step(n[:, :, 1:], t, latents[:, :, 1:], **extra).prev_sample
         return latents
 
     @staticmethod

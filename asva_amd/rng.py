@@ -40,6 +40,16 @@ class DeviceGenerator:
         self.streams += 1
         return s
 
+    def take_streams(self, n: int) -> int:
+        """`n` consecutive fresh stream ids; returns the first.  A stochastic sampler takes one per batch row of a clip and draws
+        row b's noise of step i as (stream + b, step i)."""
+        n = int(n)
+        if n < 0 or self.streams + n > 1 << 32:
+            raise RuntimeError(f"DeviceGenerator: {n} more streams are not left in the 2^32 of this seed; reseed")
+        s = self.streams
+        self.streams += n
+        return s
+
     def normal(self, shape, device="cuda", stream: Optional[int] = None, step: int = 0) -> torch.Tensor:
         """f32 normals of `shape` on `device`: element i (row-major) is normal i of (seed, stream, step); `stream=None` takes a
         fresh stream"""

@@ -11,7 +11,8 @@ skip_prk_steps true, set_alpha_to_one false, epsilon prediction, "leading" times
 Every class has two forms of the same arithmetic:
   * the object protocol of the reference pipeline (`set_timesteps`, `timesteps`, `init_noise_sigma`, `scale_model_input`,
     `step(...).prev_sample`), tensor-level on any device, so that it drops into AudioCondAnimationPipeline;
-  * the fast path: `plan_step(i)` turns step i into a plan of scalars (StepPlan, MultistepPlan or UniPCPlan), and the plan is the
+  * the fast path: `plan_step(i)` turns step i into a plan of scalars (StepPlan, MultistepPlan or UniPCPlan; NoisyStepPlan and
+    NoisyMultistepPlan for DDIM with eta > 0 and SDE-DPM-Solver++, whose kernels draw the step's noise themselves), and the plan is the
     seam to everything below it.  `plan.launch(ops, ...)` makes the one kernel launch that folds guidance, the update and frame-0
     pinning (ops.guided_step / guided_multistep / guided_unipc; the history ring stays on the device), and `plan.record(t)` is
     the plan's line in the table a Python-free host replays (asva_amd/plan.py, tools/plan_host.cpp).  DenoiseEngine, the
@@ -19,6 +20,7 @@ Every class has two forms of the same arithmetic:
 """
 from __future__ import annotations
 
+import inspect
 import math
 import struct
 from dataclasses import dataclass, field
@@ -98,6 +100,47 @@ class MultistepPlan:
         """f32 t, ca, c_cur, s_x, s_e; i32 store_slot, n_hist; i32 hist_idx[4]; f32 hist_w[4]  (60 bytes; plan_host's `denoise_ms`)"""
         return struct.pack("<5f2i4i4f", float(t), float(self.ca), float(self.c_cur), float(self.s_x), float(self.s_e),
                            int(self.store_slot), len(self.hist_idx), *_pad4(self.hist_idx, 0), *_pad4(self.hist_w, 0.0))
+
+
+@dataclass
+class NoisyStepPlan(StepPlan):
+    """Everything avsd_guided_step_sde needs for one scheduler step (DDIM with eta > 0): StepPlan's update plus c_noise * z on
+    frames 1.., z the normals (seed, stream0 + batch row, noise_step) that the kernel evaluates itself.  The key (seed, stream0)
+    belongs to the run, not to the step: `launch` reads it from `bufs._noise_key` (DenoiseEngine.prepare takes the streams)."""
+    c_noise: float = 0.0      # sigma_t of the DDIM update
+    noise_step: int = 0       # the `step` index of this step's normals: the index of the step in the run
+    noisy = True
+
+    def launch(self, ops, noise, n_branch, g, g2, x, bufs) -> None:
+        seed, stream0 = bufs._noise_key
+        if self.save_sample:
+            ops.copy(x, bufs._saved)
+        ops.guided_step_sde(noise, n_branch, g, bufs._saved if self.use_saved_sample else x, x, self.ca, self.cb, eps_hist=bufs._hist,
+                            store_slot=self.store_slot, w_cur=self.w_cur, hist_idx=self.hist_idx, w=self.hist_w, g2=g2,
+                            c_noise=self.c_noise, seed=seed, stream=stream0, step=self.noise_step)
+
+    def record(self, t) -> bytes:
+        """StepPlan's line, then f32 c_noise, u32 noise_step  (72 bytes; plan_host's `denoise_sde`)"""
+        return super().record(t) + struct.pack("<fI", float(self.c_noise), int(self.noise_step))
+
+
+@dataclass
+class NoisyMultistepPlan(MultistepPlan):
+    """Everything avsd_guided_multistep_sde needs for one scheduler step (SDE-DPM-Solver++): MultistepPlan's update plus
+    c_noise * z on frames 1.., keyed as in NoisyStepPlan."""
+    c_noise: float = 0.0      # sigma_t sqrt(1 - e^{-2h}); 0 on a step that adds no noise (final sigma 0, h = 0)
+    noise_step: int = 0
+    noisy = True
+
+    def launch(self, ops, noise, n_branch, g, g2, x, bufs) -> None:
+        seed, stream0 = bufs._noise_key
+        ops.guided_multistep_sde(noise, n_branch, g, x, x, self.ca, self.c_cur, self.s_x, self.s_e, hist=bufs._hist,
+                                 store_slot=self.store_slot, hist_idx=self.hist_idx, w=self.hist_w, g2=g2, c_noise=self.c_noise,
+                                 seed=seed, stream=stream0, step=self.noise_step)
+
+    def record(self, t) -> bytes:
+        """MultistepPlan's line, then f32 c_noise, u32 noise_step  (68 bytes; plan_host's `denoise_ms_sde`)"""
+        return super().record(t) + struct.pack("<fI", float(self.c_noise), int(self.noise_step))
 
 
 @dataclass
@@ -200,6 +243,27 @@ class _Scheduler(_ForwardProcess):
     def num_forwards(self) -> int:
         return len(self._ts)
 
+    # a stochastic sampler (DDIM eta > 0, SDE-DPM-Solver++) overrides this; the pipeline then hands it a DeviceGenerator
+    stochastic = False
+
+    def _step_noise(self, i: int, model_output, sample, generator, variance_noise):
+        """The noise of step i of the object protocol.  `variance_noise` wins.  A DeviceGenerator gives batch row b the normals
+        (s0 + b, step i) in the shape of a row of `sample`, s0 the first of sample.shape[0] streams taken at the first step after
+        `set_timesteps`: on the (B, C, F - 1, H, W) slice of the reference loop these are the normals the fused step kernels evaluate.
+        Any other generator, or None, draws torch.randn as diffusers' randn_tensor does."""
+        if variance_noise is not None:
+            return variance_noise
+        from .rng import DeviceGenerator
+
+        if isinstance(generator, DeviceGenerator):
+            if self.__dict__.get("_noise_stream0") is None:
+                self._noise_stream0 = generator.take_streams(sample.shape[0])
+            dev = sample.device if sample.is_cuda else "cuda"              # drawn on the device; a host sample gets a copy
+            rows = [generator.normal(tuple(sample.shape[1:]), device=dev, stream=self._noise_stream0 + b, step=i)
+                    for b in range(sample.shape[0])]
+            return torch.stack(rows).to(device=sample.device, dtype=sample.dtype)
+        return torch.randn(model_output.shape, generator=generator, device=model_output.device, dtype=model_output.dtype)
+
     @classmethod
     def from_pretrained(cls, path: str, subfolder: Optional[str] = None):
         return cls.from_config(_read_config(path, subfolder))
@@ -246,9 +310,42 @@ class _Base(_Scheduler):
 
 
 class DDIMScheduler(_Base):
-    """eta = 0, no clipping / thresholding: x' = sqrt(a'/a) x + (sqrt(1-a') - sqrt(a'(1-a)/a)) eps."""
+    """No clipping / thresholding.  eta = 0: x' = sqrt(a'/a) x + (sqrt(1-a') - sqrt(a'(1-a)/a)) eps.  eta > 0 (Song et al. 2020,
+    eq. 12 and 16, as diffusers' DDIMScheduler.step writes it): with var = (1-a')/(1-a) (1 - a/a') and sigma = eta sqrt(var),
+    x' = sqrt(a'/a) x + (sqrt(1-a'-sigma^2) - sqrt(a'(1-a)/a)) eps + sigma z; eta = 1 is the ancestral (DDPM) sampler.
+
+    `step(..., eta=)` takes eta per call as diffusers does.  The fast path reads `self.eta` (0.0 until `set_eta`); eta is not a
+    constructor or configuration key, as in diffusers."""
+
+    eta = 0.0
+
+    def set_eta(self, eta: float) -> "DDIMScheduler":
+        eta = float(eta)
+        if not eta >= 0.0:
+            raise ValueError(f"DDIM eta must be >= 0, got {eta}")
+        self.eta = eta
+        return self
+
+    @property
+    def stochastic(self) -> bool:
+        return self.eta != 0.0
+
+    def _coeffs(self, i: int, eta: float) -> Tuple[float, float, float]:
+        """(ca, cb, sigma) of step i: x' = ca x + cb eps + sigma z"""
+        if not eta >= 0.0:
+            raise ValueError(f"DDIM eta must be >= 0, got {eta}")
+        t = self._ts[i]
+        prev = t - self.num_train_timesteps // self.num_inference_steps
+        a, ap = self._acp(t), self._acp(prev)
+        var = (1.0 - ap) / (1.0 - a) * (1.0 - a / ap)
+        sigma = eta * var ** 0.5
+        room = 1.0 - ap - sigma * sigma
+        if room < 0.0:
+            raise ValueError(f"DDIM eta {eta}: step {i} has 1 - a' - sigma^2 = {room} < 0")
+        return (ap / a) ** 0.5, room ** 0.5 - (ap * (1.0 - a) / a) ** 0.5, sigma
 
     def set_timesteps(self, num_inference_steps: int, device=None):
+        self._noise_stream0 = None
         self.num_inference_steps = num_inference_steps
         ratio = self.num_train_timesteps // num_inference_steps
         ts = (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64) + self.steps_offset
@@ -256,19 +353,18 @@ class DDIMScheduler(_Base):
         self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
 
     def plan_step(self, i: int) -> StepPlan:
-        t = self._ts[i]
-        prev = t - self.num_train_timesteps // self.num_inference_steps
-        a, ap = self._acp(t), self._acp(prev)
-        ca = (ap / a) ** 0.5
-        cb = (1.0 - ap) ** 0.5 - (ap * (1.0 - a) / a) ** 0.5
-        return StepPlan(ca=ca, cb=cb)
+        ca, cb, sigma = self._coeffs(i, self.eta)
+        if self.eta == 0.0:
+            return StepPlan(ca=ca, cb=cb)
+        return NoisyStepPlan(ca=ca, cb=cb, c_noise=sigma, noise_step=i)
 
-    def step(self, model_output, timestep, sample, eta: float = 0.0, generator=None, return_dict=True, **_):
-        if eta != 0.0:
-            raise NotImplementedError("DDIM eta != 0")
+    def step(self, model_output, timestep, sample, eta: float = 0.0, use_clipped_model_output: bool = False, generator=None,
+             variance_noise=None, return_dict=True, **_):
         i = self._ts.index(int(timestep))
-        p = self.plan_step(i)
-        prev = p.ca * sample + p.cb * model_output
+        ca, cb, sigma = self._coeffs(i, float(eta))
+        prev = ca * sample + cb * model_output
+        if eta != 0.0:
+            prev = prev + sigma * self._step_noise(i, model_output, sample, generator, variance_noise)
         return _Output(prev) if return_dict else (prev,)
 
 
@@ -471,8 +567,10 @@ class _Multistep(_Scheduler):
 class DPMSolverMultistepScheduler(_Multistep):
     """DPM-Solver++ (Lu et al. 2022, arXiv:2211.01095), multistep, orders 1-3, restated from diffusers 0.29.2's
     `DPMSolverMultistepScheduler` (`set_timesteps`, `convert_model_output`, `dpm_solver_first_order_update`,
-    `multistep_dpm_solver_second_order_update`, `multistep_dpm_solver_third_order_update`, `step`) for the deterministic
-    data-prediction solver on an epsilon-predicting model.
+    `multistep_dpm_solver_second_order_update`, `multistep_dpm_solver_third_order_update`, `step`) for the data-prediction
+    solver on an epsilon-predicting model.  This class is the deterministic solver (algorithm_type="dpmsolver++", the only value
+    its constructor takes; `from_config` maps an SDE configuration back to it); SDEDPMSolverMultistepScheduler below is its
+    stochastic form at orders 1 and 2 and overrides the update itself (`_coeffs_sde`, `plan_step`, `step`).
 
     With sigma = sqrt((1 - acp) / acp), alpha_t = 1 / sqrt(1 + sigma^2), sigma_t = sigma * alpha_t and
     lambda = log(alpha_t) - log(sigma_t), step i turns eps into the data prediction x0 = (x - sigma_t eps) / alpha_t and moves x
@@ -495,11 +593,12 @@ class DPMSolverMultistepScheduler(_Multistep):
       * the third-order update is the published one (D2 = (D1_0 - D1_1) / (r0 + r1) times -alpha_t phi_3).  It weighs the
         second-derivative term at half of a third-order Taylor match, so on an exactly solvable problem 3M converges at order 2,
         with a smaller constant than 2M (tests/test_dpmsolver_cpu.py measures both).
-    Every other option that changes the samples (SDE variants, thresholding, v- / sample prediction, variance_type,
+    Every other option that changes the samples (the other algorithm types, thresholding, v- / sample prediction, variance_type,
     euler_at_final, lambda_min_clipped, Lu lambdas, rescale_betas_zero_snr, trained_betas) raises NotImplementedError.
     """
 
     SOLVER_TYPES = ("midpoint", "heun")
+    ALGORITHM_TYPES: Tuple[str, ...] = ("dpmsolver++",)
     # keys of the SD1.5 PNDM / DDIM configurations that DPM-Solver++ does not have
     KNOWN_INERT = frozenset({"skip_prk_steps", "set_alpha_to_one", "clip_sample", "clip_sample_range"})
     CONFIG_KEYS = ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "solver_order", "prediction_type",
@@ -512,14 +611,21 @@ class DPMSolverMultistepScheduler(_Multistep):
                  euler_at_final=False, use_karras_sigmas=False, use_lu_lambdas=False, final_sigmas_type="zero",
                  lambda_min_clipped=-float("inf"), variance_type=None, timestep_spacing="linspace", steps_offset=0,
                  rescale_betas_zero_snr=False, **unknown):
-        if algorithm_type != "dpmsolver++" or prediction_type != "epsilon":
-            raise NotImplementedError("only algorithm_type='dpmsolver++' with prediction_type='epsilon' is restated")
+        if algorithm_type not in self.ALGORITHM_TYPES or prediction_type != "epsilon":
+            raise NotImplementedError(f"{type(self).__name__}: only algorithm_type {' / '.join(map(repr, self.ALGORITHM_TYPES))} with "
+                                      "prediction_type='epsilon' is restated (SDEDPMSolverMultistepScheduler is 'sde-dpmsolver++')")
+        self.algorithm_type = algorithm_type
         refused = (thresholding or euler_at_final or use_lu_lambdas or variance_type is not None or rescale_betas_zero_snr
                    or trained_betas is not None or lambda_min_clipped != -float("inf"))
         super().__init__(num_train_timesteps, beta_start, beta_end, beta_schedule, solver_order, solver_type, lower_order_final,
                          use_karras_sigmas, final_sigmas_type, timestep_spacing, steps_offset,
                          refused and "thresholding / euler_at_final / use_lu_lambdas / variance_type / lambda_min_clipped / "
                                      "rescale_betas_zero_snr / trained_betas are not restated", unknown, algorithm_type=algorithm_type)
+
+    @staticmethod
+    def _adopt(cfg: dict) -> dict:
+        """the configuration of an SDEDPMSolverMultistepScheduler becomes this class's: the diffusers idiom for switching back"""
+        return dict(cfg, algorithm_type="dpmsolver++") if cfg.get("algorithm_type") == "sde-dpmsolver++" else cfg
 
     def _coeffs(self, i: int):
         """x' = ca x + c0 D0 + c1 D1 + c2 D2 for the step sigmas[i] -> sigmas[i + 1], and the ratios r0 = h_0 / h, r1 = h_1 / h of
@@ -587,6 +693,88 @@ class DPMSolverMultistepScheduler(_Multistep):
             D1 = D1_0 + (r0 / (r0 + r1)) * (D1_0 - D1_1)
             D2 = (1.0 / (r0 + r1)) * (D1_0 - D1_1)
             prev_sample = ca * sample + c0 * m[-1] + c1 * D1 + c2 * D2
+        return self._end_step(prev_sample, return_dict)
+
+
+class SDEDPMSolverMultistepScheduler(DPMSolverMultistepScheduler):
+    """SDE-DPM-Solver++ (diffusers' `DPMSolverMultistepScheduler(algorithm_type="sde-dpmsolver++")`; Lu et al. 2022, the SDE form of
+    the data-prediction solver), orders 1 and 2, midpoint and heun; order 3 raises, because no third-order SDE update is published
+    and diffusers has none.  With h = lambda_t - lambda_s and D1 = (m0 - m1) / r0:
+
+        x' = (sigma_t / sigma_s e^-h) x + alpha_t (1 - e^-2h) D0 + cD D1 + sigma_t sqrt(1 - e^-2h) z
+        cD = alpha_t (1 - e^-2h) / 2 (midpoint)  or  alpha_t ((1 - e^-2h) / (-2h) + 1) (heun)
+
+    A class of its own and not an option of DPMSolverMultistepScheduler: that class's constructor keeps refusing every
+    algorithm_type but "dpmsolver++", as it always has, and everything else (tables, lower-order-final logic, final sigma zero,
+    h = 0, the ring) is inherited.  `config["algorithm_type"]` is "sde-dpmsolver++"; `from_config` of another scheduler's
+    configuration replaces whatever that one says.  `plan_step` returns NoisyMultistepPlan (avsd_guided_multistep_sde draws z in
+    the launch); `step(..., generator=, variance_noise=)` draws as `_Scheduler._step_noise` says."""
+
+    ALGORITHM_TYPES = ("sde-dpmsolver++",)
+
+    def __init__(self, *args, **kw):
+        given = inspect.signature(DPMSolverMultistepScheduler.__init__).bind_partial(self, *args, **kw).arguments
+        if "algorithm_type" not in given:
+            kw["algorithm_type"] = "sde-dpmsolver++"
+        if given.get("solver_order", 2) == 3:
+            raise NotImplementedError("sde-dpmsolver++ has no third-order update (none is published; diffusers has none either)")
+        super().__init__(*args, **kw)
+
+    @staticmethod
+    def _adopt(cfg: dict) -> dict:
+        return dict(cfg, algorithm_type="sde-dpmsolver++")
+
+    stochastic = True
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        super().set_timesteps(num_inference_steps, device)
+        self._noise_stream0 = None
+
+    def _coeffs_sde(self, i: int):
+        """SDE-DPM-Solver++ (diffusers' `sde-dpmsolver++` branches): x' = ca x + c0 D0 + cd D1 + c_noise z for the step
+        sigmas[i] -> sigmas[i + 1], with q = 1 - e^{-2h}: ca = sigma_t / sigma_s e^{-h}, c0 = alpha_t q,
+        cd = alpha_t q / 2 (midpoint) or alpha_t (q / (-2h) + 1) (heun), c_noise = sigma_t sqrt(q); and r0 as in `_coeffs`.
+        cd is None on the two degenerate steps, which add no noise either."""
+        alpha_t, sigma_t = self._alpha_sigma(float(self.sigmas[i + 1]))
+        sigma_s0 = self._alpha_sigma(float(self.sigmas[i]))[1]
+        if sigma_t == 0.0:       # final sigma zero: the data prediction itself
+            return 0.0, alpha_t, None, 0.0, None
+        h = self._lambda(i + 1) - self._lambda(i)
+        if h == 0.0:             # Karras sigmas with final_sigmas_type="sigma_min": x does not move
+            return 1.0, 0.0, None, 0.0, None
+        q = -math.expm1(-2.0 * h)
+        cd = 0.5 * alpha_t * q if self.solver_type == "midpoint" else alpha_t * (q / (-2.0 * h) + 1.0)
+        r0 = (self._lambda(i) - self._lambda(i - 1)) / h if i >= 1 else None
+        return sigma_t / sigma_s0 * math.exp(-h), alpha_t * q, cd, sigma_t * math.sqrt(q), r0
+
+    def plan_step(self, i: int) -> NoisyMultistepPlan:
+        """Step i as coefficients of avsd_guided_multistep_sde; the ring is used as in the parent"""
+        last_first, _ = self._lower_order(i)
+        ca, c0, cd, c_noise, r0 = self._coeffs_sde(i)
+        slot = lambda j: j % self.solver_order  # noqa: E731
+        store = slot(i) if self.solver_order > 1 and i < len(self._ts) - 1 else -1
+        if self.solver_order == 1 or i < 1 or last_first or cd is None:
+            cur, idx, w = c0, (), ()
+        else:
+            cdr = cd / r0                                                      # D1 = (m0 - m1) / r0
+            cur, idx, w = c0 + cdr, (slot(i - 1),), (-cdr,)
+        s_x, s_e = self._scales(i)
+        return NoisyMultistepPlan(ca=ca, c_cur=cur, s_x=s_x, s_e=s_e, store_slot=store, hist_idx=idx, hist_w=w, c_noise=c_noise,
+                                  noise_step=i)
+
+    # object protocol: diffusers' step for algorithm_type="sde-dpmsolver++"
+    def step(self, model_output, timestep, sample, generator=None, variance_noise=None, return_dict=True, **_):
+        i, x0 = self._begin_step(model_output, timestep, sample)
+        last_first, _ = self._lower_order(i)
+        self.model_outputs = self.model_outputs[1:] + [x0]
+        m = self.model_outputs
+        ca, c0, cd, c_noise, r0 = self._coeffs_sde(i)
+        noise = self._step_noise(i, model_output, sample, generator, variance_noise)         # drawn at every step, as diffusers does
+        prev_sample = ca * sample + c0 * x0
+        if not (self.solver_order == 1 or self.lower_order_nums < 1 or last_first or cd is None):
+            prev_sample = prev_sample + cd * ((1.0 / r0) * (m[-1] - m[-2]))
+        if c_noise != 0.0:
+            prev_sample = prev_sample + c_noise * noise
         return self._end_step(prev_sample, return_dict)
 
 

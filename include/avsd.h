@@ -425,6 +425,27 @@ int avsd_philox4x32_u32(uint32_t* out, int64_t n_words, uint64_t seed, uint32_t 
                         void* hip_stream);
 int avsd_randn_philox_f32(float* out, int64_t n, uint64_t seed, uint32_t stream, uint32_t step, int64_t first, void* hip_stream);
 
+/* The stochastic forms of avsd_guided_step and avsd_guided_multistep (DDIM with eta > 0, SDE-DPM-Solver++): every argument of the
+ * deterministic entry point, then the noise coefficient and the key of the step's normals.  With `acc` exactly the value the
+ * deterministic entry point stores,
+ *   x_out[b, c, f, p] = fmaf(c_noise, z, acc)   for f >= 1,   x_out[:, :, 0] = x_in[:, :, 0] bit-exact,
+ * where z is normal j = (c (F - 1) + (f - 1)) HW + p (64-bit) of the sequence (seed, stream + b, step) above: block j >> 2, lane
+ * j & 3.  The noise of batch row b is therefore avsd_randn_philox_f32(C (F - 1) HW, seed, stream + b, step) laid out as
+ * (C, F - 1, H, W), the slice a loop hands to scheduler.step; frame 0 spends no normal, and a clip's noise does not depend on the
+ * batch it sits in.  The normals are evaluated in registers: no noise buffer, no second launch.  History stores are those of the
+ * deterministic entry points and x_in == x_out stays legal.  F == 1 copies x_in; c_noise == 0 gives the deterministic values.
+ * stream + B must not exceed 2^32 (AVSD_EINVAL).  When HW % 4 == 0 and noise_pred, the history, x_in and x_out are 16-byte
+ * aligned, a thread moves four elements of a frame row as one vector and evaluates one Philox block for them; otherwise one element
+ * per thread.  Both paths give the same bits. */
+int avsd_guided_step_sde(const float* noise_pred, int n_branch, float g, float g2, float* eps_hist, int store_slot, float w_cur,
+                         const int32_t* hist_idx_host, const float* w_host, int n_hist, const float* x_in, float* x_out,
+                         float ca, float cb, int B, int C, int F, int HW, float c_noise, uint64_t seed, uint32_t stream,
+                         uint32_t step, void* hip_stream);
+int avsd_guided_multistep_sde(const float* noise_pred, int n_branch, float g, float g2, float* hist, int store_slot,
+                              const int32_t* hist_idx_host, const float* w_host, int n_hist, const float* x_in, float* x_out,
+                              float ca, float c_cur, float s_x, float s_e, int B, int C, int F, int HW, float c_noise,
+                              uint64_t seed, uint32_t stream, uint32_t step, void* hip_stream);
+
 /* Guidance + UniPC step (corrector, then predictor) on (B, C, F, H, W) f32 latents, frame 0 pinned, one launch:
  *   eps  = guidance combine of noise_pred (n_branch 1 / 2 / 3, g, g2: exactly the rule of avsd_guided_step)
  *   d    = s_x * x_in + s_e * eps            (data prediction m_i of the PREDICTED sample x_in the UNet just saw)

@@ -19,6 +19,12 @@
 //   denoise_unipc <steps_unipc.bin> <latents> <x> <t> <noise> <n_branch> <g> <g2> <B> <C> <F> <HW>
 //                                              the same loop with a UniPC table (schedulers.UniPCPlan.record): the
 //                                              update is avsd_guided_unipc, corrector and predictor in one launch
+//   denoise_sde <steps_sde.bin> <latents> <x> <t> <noise> <n_branch> <g> <g2> <B> <C> <F> <HW> <seed> <stream0>
+//   denoise_ms_sde <steps_ms_sde.bin> <latents> <x> <t> <noise> <n_branch> <g> <g2> <B> <C> <F> <HW> <seed> <stream0>
+//                                              the stochastic forms (schedulers.NoisyStepPlan.record / NoisyMultistepPlan.record:
+//                                              the deterministic line plus f32 c_noise, u32 noise_step): the update is
+//                                              avsd_guided_step_sde / avsd_guided_multistep_sde, whose normals are a function of
+//                                              (seed, stream0 + batch row, noise_step, element), so the clip equals the engine's
 //   copy <src> <dst> <bytes>                   device-to-device between regions
 //   save <region> <file>                       download a region to a file
 // <latents>, <x>, <t>, <noise> and the names after load / save / copy are REGION names of the bundle.
@@ -63,6 +69,8 @@ struct Api {
   decltype(&avsd_guided_step) guided_step;
   decltype(&avsd_guided_multistep) guided_multistep;
   decltype(&avsd_guided_unipc) guided_unipc;
+  decltype(&avsd_guided_step_sde) guided_step_sde;
+  decltype(&avsd_guided_multistep_sde) guided_multistep_sde;
   decltype(&avsd_copy) copy;
 };
 
@@ -90,6 +98,20 @@ struct MsStep {
   int32_t hist_idx[4];
   float hist_w[4];
 };
+
+// the stochastic tables: the deterministic line, then the noise coefficient and the step index of the normals
+// (schedulers.NoisyStepPlan.record: 72 bytes; schedulers.NoisyMultistepPlan.record: 68 bytes)
+struct SdeStep {
+  Step s;
+  float c_noise;
+  uint32_t noise_step;
+};
+struct MsSdeStep {
+  MsStep m;
+  float c_noise;
+  uint32_t noise_step;
+};
+static_assert(sizeof(Step) == 64 && sizeof(MsStep) == 60 && sizeof(SdeStep) == 72 && sizeof(MsSdeStep) == 68, "step table layout");
 
 // one entry of the UniPC table (asva_amd/plan.py: export_steps; schedulers.UniPCPlan.record)
 struct UniPCStep {
@@ -135,6 +157,8 @@ int main(int argc, char** argv) {
   sym(h, "avsd_guided_step", api.guided_step);
   sym(h, "avsd_guided_multistep", api.guided_multistep);
   sym(h, "avsd_guided_unipc", api.guided_unipc);
+  sym(h, "avsd_guided_step_sde", api.guided_step_sde);
+  sym(h, "avsd_guided_multistep_sde", api.guided_multistep_sde);
   sym(h, "avsd_copy", api.copy);
 #define AVSD_OK_OR_DIE(x)                                                              \
   do {                                                                                 \
@@ -231,16 +255,25 @@ int main(int argc, char** argv) {
       long long bytes;
       ss >> s >> d >> bytes;
       AVSD_OK_OR_DIE(api.copy(reg(s).ptr, reg(d).ptr, bytes, 1, stream));
-    } else if (cmd == "denoise" || cmd == "denoise_ms" || cmd == "denoise_unipc") {
-      const bool dpm = cmd == "denoise_ms", unipc = cmd == "denoise_unipc";
+    } else if (cmd == "denoise" || cmd == "denoise_ms" || cmd == "denoise_unipc" || cmd == "denoise_sde" || cmd == "denoise_ms_sde") {
+      const bool sde = cmd == "denoise_sde" || cmd == "denoise_ms_sde";
+      const bool dpm = cmd == "denoise_ms" || cmd == "denoise_ms_sde", unipc = cmd == "denoise_unipc";
       std::string file, lat, x, t, noise;
       int n_branch, B, Cc, Fr, HW;
       float g, g2;
       ss >> file >> lat >> x >> t >> noise >> n_branch >> g >> g2 >> B >> Cc >> Fr >> HW;
+      unsigned long long seed = 0, stream0 = 0;
+      if (sde && (!(ss >> seed >> stream0) || stream0 > 0xffffffffull)) {
+        fprintf(stderr, "plan_host: %s: needs <seed> <stream0> (64 and 32 bits, unsigned) after <HW>\n", cmd.c_str());
+        return 1;
+      }
       const std::vector<unsigned char> raw = read_file(file);
-      const size_t n = raw.size() / (unipc ? sizeof(UniPCStep) : dpm ? sizeof(MsStep) : sizeof(Step));
-      const Step* steps = reinterpret_cast<const Step*>(raw.data());
-      const MsStep* ms_steps = reinterpret_cast<const MsStep*>(raw.data());
+      const size_t rec = unipc ? sizeof(UniPCStep) : sde ? (dpm ? sizeof(MsSdeStep) : sizeof(SdeStep)) : dpm ? sizeof(MsStep) : sizeof(Step);
+      const size_t n = raw.size() / rec;
+      if (sde && raw.size() % rec != 0) {
+        fprintf(stderr, "plan_host: %s: %s is not a table of %zu-byte records\n", cmd.c_str(), file.c_str(), rec);
+        return 1;
+      }
       const UniPCStep* up_steps = reinterpret_cast<const UniPCStep*>(raw.data());
       const int64_t lat_bytes = (int64_t)B * Cc * Fr * HW * 4;
       float *hist = nullptr, *saved = nullptr;
@@ -278,7 +311,8 @@ int main(int argc, char** argv) {
       HIP_OK(hipEventRecord(e0, stream));
       for (size_t i = 0; i < n; ++i) {
         AVSD_OK_OR_DIE(api.copy(latents, xp, lat_bytes, 1, stream));
-        HIP_OK(hipMemcpyAsync(tp, unipc ? &up_steps[i].t : dpm ? &ms_steps[i].t : &steps[i].t, 4, hipMemcpyHostToDevice, stream));
+        // every record starts with its timestep
+        HIP_OK(hipMemcpyAsync(tp, raw.data() + i * rec, 4, hipMemcpyHostToDevice, stream));
         if (gexec) HIP_OK(hipGraphLaunch(gexec, stream));
         else AVSD_OK_OR_DIE(api.run(b, kf, stream));
         if (unipc) {
@@ -296,23 +330,38 @@ int main(int argc, char** argv) {
           continue;
         }
         if (dpm) {
-          const MsStep& m = ms_steps[i];
+          MsSdeStep mz{};
+          memcpy(&mz, raw.data() + i * rec, rec);       // the deterministic record is a prefix of the stochastic one
+          const MsStep& m = mz.m;
           bool ok = m.store_slot < 4 && m.n_hist >= 0 && m.n_hist <= 4;
           for (int k = 0; ok && k < m.n_hist; ++k) ok = m.hist_idx[k] >= 0 && m.hist_idx[k] < 4;
           if (!ok) {
             fprintf(stderr, "plan_host: %s step %zu names a history slot outside the 4-slot ring\n", file.c_str(), i);
             return 1;
           }
-          AVSD_OK_OR_DIE(api.guided_multistep(np_, n_branch, g, g2, hist, m.store_slot, m.n_hist ? m.hist_idx : nullptr,
-                                              m.n_hist ? m.hist_w : nullptr, m.n_hist, latents, latents, m.ca, m.c_cur, m.s_x,
-                                              m.s_e, B, Cc, Fr, HW, stream));
+          if (sde)
+            AVSD_OK_OR_DIE(api.guided_multistep_sde(np_, n_branch, g, g2, hist, m.store_slot, m.n_hist ? m.hist_idx : nullptr,
+                                                    m.n_hist ? m.hist_w : nullptr, m.n_hist, latents, latents, m.ca, m.c_cur, m.s_x,
+                                                    m.s_e, B, Cc, Fr, HW, mz.c_noise, seed, (uint32_t)stream0, mz.noise_step, stream));
+          else
+            AVSD_OK_OR_DIE(api.guided_multistep(np_, n_branch, g, g2, hist, m.store_slot, m.n_hist ? m.hist_idx : nullptr,
+                                                m.n_hist ? m.hist_w : nullptr, m.n_hist, latents, latents, m.ca, m.c_cur, m.s_x,
+                                                m.s_e, B, Cc, Fr, HW, stream));
           continue;
         }
-        const Step& s = steps[i];
+        SdeStep sz{};
+        memcpy(&sz, raw.data() + i * rec, rec);
+        const Step& s = sz.s;
         if (s.save_sample) AVSD_OK_OR_DIE(api.copy(latents, saved, lat_bytes, 1, stream));
-        AVSD_OK_OR_DIE(api.guided_step(np_, n_branch, g, g2, hist, s.store_slot, s.w_cur,
-                                       s.n_hist ? s.hist_idx : nullptr, s.n_hist ? s.hist_w : nullptr, s.n_hist,
-                                       s.use_saved ? saved : latents, latents, s.ca, s.cb, B, Cc, Fr, HW, stream));
+        if (sde)
+          AVSD_OK_OR_DIE(api.guided_step_sde(np_, n_branch, g, g2, hist, s.store_slot, s.w_cur,
+                                             s.n_hist ? s.hist_idx : nullptr, s.n_hist ? s.hist_w : nullptr, s.n_hist,
+                                             s.use_saved ? saved : latents, latents, s.ca, s.cb, B, Cc, Fr, HW, sz.c_noise, seed,
+                                             (uint32_t)stream0, sz.noise_step, stream));
+        else
+          AVSD_OK_OR_DIE(api.guided_step(np_, n_branch, g, g2, hist, s.store_slot, s.w_cur,
+                                         s.n_hist ? s.hist_idx : nullptr, s.n_hist ? s.hist_w : nullptr, s.n_hist,
+                                         s.use_saved ? saved : latents, latents, s.ca, s.cb, B, Cc, Fr, HW, stream));
       }
       HIP_OK(hipEventRecord(e1, stream));
       HIP_OK(hipStreamSynchronize(stream));

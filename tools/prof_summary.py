@@ -1,5 +1,6 @@
 """Summarise a rocprofv3 (rocpd sqlite) kernel trace: per-kernel count, total/avg time, share.
     python tools/prof_summary.py gpurun_out/prof_xxx/name_results.db [--steps N] > profiles/xxx.md
+    python tools/prof_summary.py <db> --match 'guided_|philox'      # every kernel whose name matches, however small its share
 Template arguments of the gemm kernels are decoded into readable tile names."""
 import re
 import sqlite3
@@ -40,6 +41,7 @@ def main():
     cur = db.cursor()
     cols = [r[1] for r in cur.execute("pragma table_info(kernels)")]
     name_col = "name" if "name" in cols else [c for c in cols if "name" in c][0]
+    match = re.compile(sys.argv[sys.argv.index("--match") + 1]) if "--match" in sys.argv else None
     by_grid = "--by-grid" in sys.argv          # one row per (kernel, grid): the grid tells the shapes of one kernel apart
     gcols = [c for c in ("grid_x", "grid_y", "grid_z", "grid_size_x", "grid_size_y", "grid_size_z") if c in cols] if by_grid else []
     if by_grid and not gcols:
@@ -54,7 +56,9 @@ def main():
     total = sum(v[1] for v in agg.values())
     print(f"| kernel | launches | total us | avg us | share |")
     print(f"|---|---:|---:|---:|---:|")
-    for k, (n, us) in sorted(agg.items(), key=lambda kv: -kv[1][1])[:(120 if by_grid else 40)]:
+    ranked = sorted(agg.items(), key=lambda kv: -kv[1][1])
+    ranked = [kv for kv in ranked if match.search(kv[0])] if match else ranked[:(120 if by_grid else 40)]
+    for k, (n, us) in ranked:
         print(f"| `{k}` | {n} | {us:.0f} | {us / n:.2f} | {100 * us / total:.1f}% |")
     print(f"\ntotal kernel time {total / 1e3:.2f} ms over {sum(v[0] for v in agg.values())} launches" +
           (f"; {total / 1e3 / steps:.3f} ms per step over {steps} steps (all kernels incl. warm-up/autotune)" if steps else ""))
