@@ -162,6 +162,10 @@ SIGNATURES = {
     "avsd_mean_rows_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "avsd_resize_aa_normalize_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                              c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_float] * 6 + [c_void_p]),
+    # AVSync classifier on a matrix of pairs (csrc/avsync_pairs.hip): f32 in both builds
+    "avsd_pair_head_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                   c_void_p]),
+    "avsd_pair_xent_f32": (c_int, [c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     # CLIP text encoder (csrc/clip_text.hip): f32 in both builds
     "avsd_embed_tokens_f32": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
     "avsd_layernorm_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p]),

@@ -9,12 +9,18 @@ scale at pack time, is one `avsd_convnd_f32` launch.
 Everything is f32 on the f32-input matrix cores, in the bf16 and the fp16 build of the library alike: a score must not move with
 the storage mode of the clip it judges.  No host synchronisation inside `forward`; all launches go to the current stream.
 
+Also here, what the reference does with the classifier beyond scoring aligned rows, all of it the FC head on a MATRIX of pairs
+(csrc/avsync_pairs.hip): `AVSyncClassifier.pair_scores`, the contrastive objective of avsync/models/sync_contrastive_trainer.py
+(`AVSyncContrastiveTrainer`, forward values only) and the shift-accuracy evaluation of scripts/avsync_eval.py (`shifted_pairs`,
+`shift_accuracy`, `evaluate_shift_accuracy`; tools/avsync_eval.py).
+
 No trained classifier checkpoint was available when this was written: the path is pinned against the reference's modules with
-seeded weights (tests/golden/avsync_tiny.pt), and no RelSync value of a real clip has been measured.
+seeded weights (tests/golden/avsync_tiny.pt), and no RelSync value or shift accuracy of a real checkpoint has been measured.
 """
 from __future__ import annotations
 
 import os
+import random
 from typing import Dict, Optional
 
 import numpy as np
@@ -192,6 +198,18 @@ class _Hip(f32net._HipBase):
 
     maxpool = staticmethod(ops.maxpool_hw_f32)
 
+    @staticmethod
+    def half(x, layer, col, bias):
+        """x [m, cin] -> x @ layer.w[:, col:col + cin].T + bias, no activation: one column half of a layer that reads a concatenation"""
+        m, cin = x.shape
+        return ops.convnd_f32(x.view(m, 1, 1, 1, cin), layer.w, (1, 1, 1), (1, 1, 1), (0, 0, 0), bias=bias, w_col=col).view(m, -1)
+
+    @staticmethod
+    def pair_head(u, vh, l2, l3):
+        return ops.pair_head_f32(u, vh, l2.w, l2.bias, l3.w, l3.bias)
+
+    pair_xent = staticmethod(ops.pair_xent_f32)
+
 
 def run_video(pk: _Pk, x: torch.Tensor, be=_Hip, stages: Optional[list] = None) -> torch.Tensor:
     """x [n, t, h, w, 3] preprocessed, channels-last -> (n, 512).  `stages`, if a list, receives the output of conv1 (after the
@@ -226,6 +244,24 @@ def run_head(pk: list, audio_emb: torch.Tensor, video_emb: torch.Tensor, be=_Hip
     for layer in pk:
         y = be.conv(y, layer)
     return y.view(y.shape[0], -1)
+
+
+def run_pair_head(pk: list, audio_emb: torch.Tensor, video_emb: torch.Tensor, be=_Hip) -> torch.Tensor:
+    """audio_emb (G, P, D), video_emb (G, Q, D) -> scores (G, P, Q): the head on every (audio p, video q) pair of each group.
+    The first layer is linear in cat(a, v): W1 . cat(a_p, v_q) + b1 = Wa . a_p + (Wv . v_q + b1), two launches on the G (P + Q)
+    distinct rows; one more launch (avsd_pair_head_f32) does the rest, and neither the (G P Q, 2 D) concatenation nor the
+    (G P Q, H1) hidden layer exists.  A head the kernel is not built for (ops.pair_head_supported) goes through `run_head` on the
+    materialised pairs: one route per head size, so a score is a function of its pair alone either way."""
+    G, P, D = audio_emb.shape
+    Q = video_emb.shape[1]
+    if len(pk) == 3 and pk[0].cin == 2 * D and pk[0].relu and pk[1].relu and ops.pair_head_supported(D, pk[0].cout, pk[1].cout):
+        l1, l2, l3 = pk
+        u = be.half(audio_emb.reshape(G * P, D), l1, 0, None).view(G, P, -1)
+        vh = be.half(video_emb.reshape(G * Q, D), l1, D, l1.bias).view(G, Q, -1)
+        return be.pair_head(u, vh, l2, l3)
+    a = audio_emb[:, :, None, :].expand(G, P, Q, D).reshape(G * P * Q, D)
+    v = video_emb[:, None, :, :].expand(G, P, Q, D).reshape(G * P * Q, D)
+    return run_head(pk, a, v, be)[:, 0].reshape(G, P, Q)
 
 
 class AVSyncClassifier(f32net.F32Net):
@@ -276,6 +312,19 @@ class AVSyncClassifier(f32net.F32Net):
     @torch.no_grad()
     def score_embeddings(self, audio_emb: torch.Tensor, video_emb: torch.Tensor) -> torch.Tensor:
         return run_head(self.pack(audio_emb.device).head, audio_emb, video_emb)[:, 0]
+
+    @torch.no_grad()
+    def pair_scores(self, audio_emb: torch.Tensor, video_emb: torch.Tensor, be=_Hip) -> torch.Tensor:
+        """audio_emb (G, P, D), video_emb (G, Q, D) -> scores (G, P, Q) f32: scores[g, p, q] is the head on (audio p, video q) of
+        group g.  Three launches whatever P and Q (`run_pair_head`).  `be`: the backend, as in `run_head`; one that is not the device
+        library folds the head from the module's own tensors and runs where they are."""
+        if audio_emb.dim() != 3 or video_emb.dim() != 3 or audio_emb.shape[0] != video_emb.shape[0] or audio_emb.shape[2] != video_emb.shape[2]:
+            raise ValueError(f"pair_scores: audio_emb must be (G, P, D) and video_emb (G, Q, D), got {tuple(audio_emb.shape)} and "
+                             f"{tuple(video_emb.shape)}")
+        if audio_emb.numel() == 0 or video_emb.numel() == 0:
+            raise ValueError("pair_scores: empty embeddings")
+        head = self.pack(audio_emb.device).head if be is _Hip else fold_head(self.head)
+        return run_pair_head(head, audio_emb.float().contiguous(), video_emb.float().contiguous(), be)
 
     @torch.no_grad()
     def forward(self, audio: torch.Tensor, video: torch.Tensor) -> torch.Tensor:
@@ -452,3 +501,199 @@ def compute_sync_metrics_on_av(audio_waveform: torch.Tensor, audio_sr: int, vide
     if ref_audio_waveform is not None:
         return compute_relsync(audio, video, net, ref_audios=mel(ref_audio_waveform))[0]
     return compute_relsync(audio, video, net, ref_videos=ref_video.unsqueeze(0).to(device=device, dtype=dtype))[0]
+
+
+# ---- the classifier's own objective and evaluation: the head on a matrix of pairs --------------------------------------------------
+def _embed_pairs(net: AVSyncClassifier, audios: torch.Tensor, videos: torch.Tensor, be):
+    """audios (b, k, 1, n, t), videos (b, k, 3, f, h, w) -> embeddings (b, k, D) each: all b k clips in one pass per network"""
+    if audios.dim() != 5 or videos.dim() != 6 or tuple(audios.shape[:2]) != tuple(videos.shape[:2]):
+        raise ValueError(f"audios must be (b, k, 1, n, t) and videos (b, k, 3, f, h, w) with the same b and k, got {tuple(audios.shape)} and "
+                         f"{tuple(videos.shape)}")
+    b, k = audios.shape[:2]
+    a, v = net._audio_cl(audios.flatten(0, 1)), net._video_cl(videos.flatten(0, 1))
+    if be is _Hip:
+        pk = net.pack(audios.device)
+        fa, fv = pk.audio, pk.video
+    else:
+        fa, fv = fold_audio(net.audio_encoder), fold_video(net.video_encoder)
+    return run_audio(fa, a, be).view(b, k, -1), run_video(fv, v, be).view(b, k, -1)
+
+
+class AVSyncContrastiveTrainer(nn.Module):
+    """avsync/models/sync_contrastive_trainer.py:9-60: the classifier's contrastive objective.  `forward` runs the head on all k x k
+    (audio p, video q) pairs of each example and returns (av_loss, va_loss, av_acc, va_acc): the cross-entropy of every audio over
+    the k videos and of every video over the k audios, both with the aligned pair as the label and logits divided by `tau`, and the
+    two top-1 accuracies.
+
+    VALUES ONLY: the launches carry no autograd graph, so the four results are 0-d f32 device tensors without gradient.  This is the
+    forward value of the objective (validation, monitoring, checking a checkpoint), not a training step."""
+
+    def __init__(self, audio_encoder: AudioConv2DNet, video_encoder: VideoR2Plus1DNet, head: FCHead, tau: float = 1.0):
+        super().__init__()
+        self.audio_encoder = audio_encoder
+        self.video_encoder = video_encoder
+        self.head = head
+        self.tau = tau
+        self._net = [AVSyncClassifier(audio_encoder, video_encoder, head)]      # shares the modules; kept out of state_dict()
+
+    @torch.no_grad()
+    def forward(self, audios: torch.Tensor, videos: torch.Tensor, be=_Hip):
+        """audios (b, k, 1, n, t), videos (b, k, 3, f, h, w), preprocessed -> (av_loss, va_loss, av_acc, va_acc)"""
+        net = self._net[0]
+        a, v = _embed_pairs(net, audios, videos, be)
+        r = be.pair_xent(net.pair_scores(a, v, be), float(self.tau))
+        return r["av_loss"], r["va_loss"], r["av_acc"], r["va_acc"]
+
+    def save_pretrained(self, save_dir: str):
+        for name in ("audio_encoder", "video_encoder", "head"):
+            getattr(self, name).save_pretrained(os.path.join(save_dir, name))
+
+
+@torch.no_grad()
+def shift_accuracy(net: AVSyncClassifier, audios: torch.Tensor, videos: torch.Tensor, tolerate_range: int = 5, be=_Hip) -> Dict[str, torch.Tensor]:
+    """scripts/avsync_eval.py:116-148 for one batch: audios (b, k, 1, n, t) and videos (b, k, 3, f, h, w) are k clips per example, shifted
+    by a fixed step.  All b k clips are embedded once; the centre audio (index k // 2) is scored against the k videos (one
+    `pair_scores` call with P = 1) and the k audios against the centre video (one with Q = 1).  -> av_pred, va_pred (b,) int64: the
+    argmax over videos / audios (a tie goes to the lowest index), av_hit, va_hit (b,) bool: |pred - centre| <= tolerate_range."""
+    a, v = _embed_pairs(net, audios, videos, be)
+    c = a.shape[1] // 2
+    av = be.pair_xent(net.pair_scores(a[:, c:c + 1], v, be), 1.0)["row_argmax"][:, 0].long()
+    va = be.pair_xent(net.pair_scores(a, v[:, c:c + 1], be), 1.0)["col_argmax"][:, 0].long()
+    return {"av_pred": av, "va_pred": va, "av_hit": (av - c).abs() <= int(tolerate_range), "va_hit": (va - c).abs() <= int(tolerate_range)}
+
+
+def evaluate_shift_accuracy(net: AVSyncClassifier, batches, tolerate_range: int = 5, be=_Hip) -> Dict[str, float]:
+    """scripts/avsync_eval.py:111-167: `batches` yields dicts with "index" (b,) integers, "audio" (b, k, 1, n, t) and "video"
+    (b, k, 3, f, h, w).  An example index seen more than once (a loader that replaced an unreadable file, several processes) counts
+    once and its FIRST occurrence wins.  -> {"av_acc", "va_acc", "valid_examples"}"""
+    seen: Dict[int, tuple] = {}
+    for batch in batches:
+        r = shift_accuracy(net, batch["audio"], batch["video"], tolerate_range, be)
+        for i, a, v in zip(torch.as_tensor(batch["index"]).reshape(-1).tolist(), r["av_hit"].tolist(), r["va_hit"].tolist()):
+            seen.setdefault(int(i), (float(a), float(v)))
+    if not seen:
+        raise ValueError("evaluate_shift_accuracy: no examples")
+    n = len(seen)
+    return {"av_acc": sum(a for a, _ in seen.values()) / n, "va_acc": sum(v for _, v in seen.values()) / n, "valid_examples": n}
+
+
+# ---- shifted clips of one recording (avsync/data.py:21-75, 206-248), float64 on the host ---------------------------------------------
+SAMPLING_TYPES = ("random-compact", "center-compact", "random", "uniform")
+END_POINT_NUDGE = 1e-4        # seconds: a clip's first frame time moves in and its end moves back by this much
+
+
+def uniform_starts(start: float, end: float, num: int, endpoint: bool = True) -> np.ndarray:
+    """`num` equally spaced values over [start, end]: the first and last ON the end points, or (endpoint=False) every value at the
+    centre of one of `num` equal cells, i.e. both ends pulled in by half a cell"""
+    lo, hi = float(start), float(end)
+    if not endpoint:
+        half_cell = (hi - lo) / (2 * num)
+        lo, hi = lo + half_cell, hi - half_cell
+    if num == 1:
+        return np.array([lo], dtype=np.float64)
+    return lo + (hi - lo) * (np.arange(num, dtype=np.float64) / (num - 1))
+
+
+def clip_starts(start: float, end: float, num: int, gap: float, sampling: str = "center-compact", rng=None) -> np.ndarray:
+    """start times (float64 [num]) of `num` clips in [start, end]: "center-compact" / "random-compact" `gap` apart, centred or at a
+    random offset; "random" at least `gap` apart, drawn one after the other; "uniform" spread from `start` to `end` whatever `gap`.
+    `rng`: a random.Random for the two random types (a fresh one when None).  A range shorter than (num - 1) * gap is refused."""
+    if sampling not in SAMPLING_TYPES:
+        raise ValueError(f"sampling must be one of {SAMPLING_TYPES}, got {sampling!r}")
+    start, end, gap = float(start), float(end), float(gap)
+    if sampling == "uniform":
+        return uniform_starts(start, end, num, endpoint=True)
+    span = (num - 1) * gap                         # from the first start to the last
+    slack = (end - start) - span                   # what is left of the range to place the first start in
+    if slack < 0:
+        raise ValueError(f"a range of {end - start:g} s ({start:g} .. {end:g}) cannot hold {num} clip starts {gap:g} s apart")
+    if rng is None:
+        rng = random.Random()
+    steps = gap * np.arange(num, dtype=np.float64)
+    if sampling == "center-compact":
+        return (start + slack / 2.0) + steps
+    if sampling == "random-compact":
+        return rng.uniform(start, start + slack) + steps
+    # "random": clip i is drawn between the earliest time its predecessor allows and the latest that leaves room for the rest
+    starts = np.empty(num, dtype=np.float64)
+    earliest = start
+    for i in range(num):
+        starts[i] = rng.uniform(earliest, end - (num - 1 - i) * gap)
+        earliest = starts[i] + gap
+    return starts
+
+
+def clip_frame_seconds(starts: np.ndarray, video_num_frames: int = 12, video_fps: float = 6) -> np.ndarray:
+    """(k, f + 1) float64: the f frame times of every clip and, last, its end; the first is moved 1e-4 s in and the end 1e-4 s back,
+    so that rounding at the end points cannot pick a neighbour (data.py:239-243)"""
+    offsets = np.arange(video_num_frames + 1, dtype=np.float64) / video_fps
+    offsets[0] += END_POINT_NUDGE
+    offsets[-1] -= END_POINT_NUDGE
+    return np.asarray(starts, dtype=np.float64).reshape(-1, 1) + offsets
+
+
+def nearest_frames(times: np.ndarray, frame_seconds: np.ndarray) -> np.ndarray:
+    """index of the frame whose timestamp is nearest to each time; exactly between two frames the earlier one (argmin's first)"""
+    return np.abs(np.asarray(times, dtype=np.float64)[..., None] - np.asarray(frame_seconds, dtype=np.float64)).argmin(axis=-1)
+
+
+@torch.no_grad()
+def shifted_pairs(frames: torch.Tensor, frame_seconds, waveform: torch.Tensor, sample_rate: int, *, num_clips: int = 31,
+                  shift_time: float = 0.04, video_fps: float = 6, video_num_frames: int = 12, sampling: str = "center-compact", rng=None,
+                  device=None, counts: Optional[dict] = None):
+    """One recording -> the `num_clips` shifted (audio, video) clips of AudioVideoAlignedMultiPairDataset.__getitem__
+    (avsync/data.py:206-248): frames (F, 3, H, W) in [0, 1] with timestamps frame_seconds [F], waveform (c, S) at sample_rate ->
+    (audios (k, 1, 128, 204), videos (k, 3, f, 224, 224)) on the device, ready for `shift_accuracy` / AVSyncContrastiveTrainer.
+    A host-side index list plus existing device calls: every DISTINCT frame the clips use is resized and normalised once
+    (`preprocess_videos`' kernel) and then gathered; each clip's audio is the sample range [round(t0 sr), round(t1 sr)) of the
+    waveform, resampled to 16 kHz on the device when needed, then `waveform_to_melspectrogram`.  `counts`, if a dict, receives
+    "frames_resized".
+
+    KNOWN DIVERGENCE: the reference gathers whole container audio packets whose timestamp falls in the clip, which cannot be
+    reproduced without its decoder; the cut here is sample-exact instead.  The per-clip random horizontal flip (`randflip`, a training
+    augmentation the evaluation switches off) is not built."""
+    from .audio_features import resample, waveform_to_melspectrogram
+
+    if frames.dim() != 4 or frames.shape[1] != 3:
+        raise ValueError(f"frames must be (F, 3, H, W), got {tuple(frames.shape)}")
+    fs = np.asarray(frame_seconds, dtype=np.float64).reshape(-1)
+    if fs.shape[0] != frames.shape[0]:
+        raise ValueError(f"{frames.shape[0]} frames but {fs.shape[0]} timestamps")
+    if fs.shape[0] == 0:
+        raise ValueError("frames is empty")
+    if waveform.dim() != 2 or waveform.shape[1] == 0:
+        raise ValueError(f"waveform must be (channels, samples), got {tuple(waveform.shape)}")
+    sample_rate = int(sample_rate)
+    device = torch.device("cuda" if device is None else device)
+    clip_duration = video_num_frames / video_fps
+    duration = min(float(fs[-1]) + (float(fs[1] - fs[0]) if len(fs) > 1 else 0.0), waveform.shape[1] / sample_rate)
+    if duration < clip_duration + (num_clips - 1) * shift_time:
+        raise ValueError(f"a recording of {duration:.3f} s is too short for {num_clips} clips of {clip_duration:.3f} s shifted by {shift_time} s")
+    times = clip_frame_seconds(clip_starts(0.0, duration - clip_duration, num_clips, shift_time, sampling, rng), video_num_frames, video_fps)
+    # video: resize the distinct frames once, gather the clips from them
+    idx = nearest_frames(times[:, :-1], fs)                                          # (k, f)
+    used, inverse = np.unique(idx.reshape(-1), return_inverse=True)
+    if counts is not None:
+        counts["frames_resized"] = int(used.shape[0])
+    src = frames[torch.from_numpy(used)].to(device=device, dtype=torch.float32)       # (U, 3, H, W)
+    pre = preprocess_videos(src.permute(1, 0, 2, 3)[None])[0]                         # (3, U, 224, 224), a view of channels-last memory
+    videos = pre[:, torch.from_numpy(inverse).to(device)].view(3, num_clips, video_num_frames, INPUT_SIZE, INPUT_SIZE).permute(1, 0, 2, 3, 4)
+    # audio: the sample-exact range of every clip
+    audios = []
+    for t0, t1 in zip(times[:, 0], times[:, -1]):
+        cut = waveform[:, int(round(t0 * sample_rate)):int(round(t1 * sample_rate))].to(device=device, dtype=torch.float32)
+        if sample_rate != 16000:
+            cut = resample(cut.contiguous(), sample_rate, 16000, device=device)
+        audios.append(waveform_to_melspectrogram(cut, device=device))
+    return torch.stack(audios), videos
+
+
+def shifted_pairs_from_avi(filename: str, **kw):
+    """`shifted_pairs` on one of the project's own .avi files (Motion-JPEG + PCM, asva_amd/video_io.py): frame i is stamped i / fps"""
+    from .video_io import read_mjpeg_avi
+
+    video, fps, audio, audio_fps = read_mjpeg_avi(filename)
+    if audio is None:
+        raise ValueError(f"{filename}: no audio stream")
+    frames = video.permute(0, 3, 1, 2).float() / 255.0
+    return shifted_pairs(frames, np.arange(frames.shape[0], dtype=np.float64) / fps, audio, audio_fps, **kw)

@@ -81,6 +81,8 @@ const Entry kEntries[] = {
     // AVSync scorer (csrc/avsync.hip)
     AVSD_PLAN_ENTRY(avsd_convnd_f32),       AVSD_PLAN_ENTRY(avsd_maxpool_hw_f32),        AVSD_PLAN_ENTRY(avsd_mean_rows_f32),
     AVSD_PLAN_ENTRY(avsd_resize_aa_normalize_f32),
+    // AVSync classifier on a matrix of pairs (csrc/avsync_pairs.hip)
+    AVSD_PLAN_ENTRY(avsd_pair_head_f32),    AVSD_PLAN_ENTRY(avsd_pair_xent_f32),
     // Inception-v3 features for FID (asva_amd/fid.py; kernels in csrc/avsync.hip)
     AVSD_PLAN_ENTRY(avsd_convnd_ld_f32),    AVSD_PLAN_ENTRY(avsd_pool3_hw_f32),
     // I3D features for FVD (asva_amd/fvd.py; kernels in csrc/avsync.hip)

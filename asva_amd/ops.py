@@ -1814,9 +1814,11 @@ def vit_tokens(patches: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, b: i
 
 # ---- AVSync scorer (csrc/avsync.hip): f32 tensors, channels-last, the same arithmetic in both builds of the library -----------
 def convnd_f32(x: torch.Tensor, w: torch.Tensor, taps, stride, pad, *, bias: Optional[torch.Tensor] = None,
-               res: Optional[torch.Tensor] = None, rscale: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:
+               res: Optional[torch.Tensor] = None, rscale: Optional[torch.Tensor] = None, relu: bool = False,
+               w_col: int = 0) -> torch.Tensor:
     """x [n, t, h, w, cin], w [cout, ldw >= taps * cin] (tap-major, cin-minor) -> act(conv + bias + rscale * res) [n, to, ho, wo, cout];
-    see avsd_convnd_f32"""
+    see avsd_convnd_f32.  w_col > 0: the weight is the column block w[:, w_col:w_col + taps * cin] of the packed matrix (ldw stays
+    its row stride) — one half of a layer that is linear in a concatenation."""
     for t, name in ((x, "x"), (w, "w"), (bias, "bias"), (res, "res"), (rscale, "rscale")):
         if t is not None and (t.dtype != F32 or not t.is_cuda or not t.is_contiguous()):   # (a size-1 channel axis may carry any stride)
             raise ValueError(f"convnd_f32: {name} must be a contiguous f32 device tensor")
@@ -1832,8 +1834,12 @@ def convnd_f32(x: torch.Tensor, w: torch.Tensor, taps, stride, pad, *, bias: Opt
         raise ValueError(f"convnd_f32: residual {tuple(res.shape)} does not match the output {(n, to, ho, wo, cout)}")
     if any(v is not None and v.numel() != cout for v in (bias, rscale)):
         raise ValueError("convnd_f32: bias / rscale must have cout entries")
+    w_col = int(w_col)
+    # (w_col == 0 is every earlier call: a row shorter than K stays the library's refusal, with its message)
+    if w_col < 0 or (w_col > 0 and w_col + kt * kh * kw * cin > ldw):
+        raise ValueError(f"convnd_f32: columns {w_col} .. {w_col + kt * kh * kw * cin} leave the weight rows of {ldw} floats")
     out = torch.empty((n, to, ho, wo, cout), dtype=F32, device=x.device)
-    check(_lib.lib().avsd_convnd_f32(_p(x), _p(w), _p(bias), _p(res), _p(rscale), _p(out), n, ti, hi, wi, cin, to, ho, wo, cout,
+    check(_lib.lib().avsd_convnd_f32(_p(x), _p(w) + 4 * w_col, _p(bias), _p(res), _p(rscale), _p(out), n, ti, hi, wi, cin, to, ho, wo, cout,
                                      kt, kh, kw, st, sh, sw, pt, ph, pw, ldw, int(relu), _stream()), "avsd_convnd_f32")
     return out
 
@@ -1843,6 +1849,59 @@ def linear_f32(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = Non
     m = x.shape[0]
     r = None if res is None else res.view(m, 1, 1, 1, -1)
     return convnd_f32(x.view(m, 1, 1, 1, -1), w, (1, 1, 1), (1, 1, 1), (0, 0, 0), bias=b, res=r).view(m, -1)
+
+
+def pair_head_supported(D: int, H1: int, H2: int) -> bool:
+    """the head sizes avsd_pair_head_f32 is built for (the real head: 512 / 512 / 256)"""
+    return D % 32 == 0 and H1 % 32 == 0 and H2 % 32 == 0 and 0 < H2 <= 256 and D > 0 and H1 > 0
+
+
+def pair_head_f32(u: torch.Tensor, vh: torch.Tensor, w2: torch.Tensor, b2: Optional[torch.Tensor], w3: torch.Tensor,
+                  b3: Optional[torch.Tensor], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """avsd_pair_head_f32 (include/avsd.h): u [G, P, H1], vh [G, Q, H1], w2 [H2, ldw2 >= H1], b2 [H2], w3 [>= 1, ldw3 >= H2] (row 0 is
+    read), b3 [>= 1] -> scores [G, P, Q], one launch.  `out`: a contiguous f32 [G, P, Q] device tensor to write into."""
+    for t, name in ((u, "u"), (vh, "vh"), (w2, "w2"), (b2, "b2"), (w3, "w3"), (b3, "b3"), (out, "out")):
+        if t is not None and (t.dtype != F32 or not t.is_cuda or not t.is_contiguous()):
+            raise ValueError(f"pair_head_f32: {name} must be a contiguous f32 device tensor")
+    if u.dim() != 3 or vh.dim() != 3 or u.shape[0] != vh.shape[0] or u.shape[2] != vh.shape[2] or u.numel() == 0 or vh.numel() == 0:
+        raise ValueError(f"pair_head_f32: u must be [G, P, H1] and vh [G, Q, H1], got {tuple(u.shape)} and {tuple(vh.shape)}")
+    (G, Pn, H1), Q = u.shape, vh.shape[1]
+    if w2.dim() != 2 or w2.shape[1] < H1 or w3.dim() != 2 or w3.shape[1] < w2.shape[0]:
+        raise ValueError(f"pair_head_f32: w2 must be [H2, >= {H1}] and w3 [out_dim, >= H2], got {tuple(w2.shape)} and {tuple(w3.shape)}")
+    H2, ldw2 = w2.shape
+    if (b2 is not None and b2.numel() != H2) or (b3 is not None and b3.numel() < 1):
+        raise ValueError("pair_head_f32: b2 must have H2 entries and b3 at least one")
+    if out is None:
+        out = torch.empty((G, Pn, Q), dtype=F32, device=u.device)
+    elif tuple(out.shape) != (G, Pn, Q) or out.device != u.device:
+        raise ValueError(f"pair_head_f32: out must be {(G, Pn, Q)} on the inputs' device")
+    check(_lib.lib().avsd_pair_head_f32(_p(u), _p(vh), _p(w2), ldw2, _p(b2), _p(w3), _p(b3), _p(out), G, Pn, Q, H1, H2, _stream()),
+          "avsd_pair_head_f32")
+    return out
+
+
+def pair_xent_f32(scores: torch.Tensor, tau: float = 1.0) -> dict:
+    """avsd_pair_xent_f32 (include/avsd.h) on contiguous scores [G, P, Q] -> dict(row_argmax [G, P] int32, col_argmax [G, Q] int32,
+    row_loss [G, P] when P <= Q, col_loss [G, Q] when Q <= P, and when P == Q av_loss, va_loss, av_acc, va_acc as 0-d f32)."""
+    _req(scores, F32, "scores")
+    if scores.dim() != 3 or scores.numel() == 0 or not scores.is_contiguous():
+        raise ValueError(f"pair_xent_f32: scores must be a contiguous non-empty [G, P, Q], got {tuple(scores.shape)}")
+    tau = float(tau)
+    if not (tau > 0.0 and tau < float("inf")):
+        raise ValueError(f"pair_xent_f32: tau must be positive and finite, got {tau}")
+    G, Pn, Q = scores.shape
+    dev = scores.device
+    r = {"row_argmax": torch.empty((G, Pn), dtype=torch.int32, device=dev), "col_argmax": torch.empty((G, Q), dtype=torch.int32, device=dev)}
+    if Pn <= Q:
+        r["row_loss"] = torch.empty((G, Pn), dtype=F32, device=dev)
+    if Q <= Pn:
+        r["col_loss"] = torch.empty((G, Q), dtype=F32, device=dev)
+    means = torch.empty((4,), dtype=F32, device=dev) if Pn == Q else None
+    check(_lib.lib().avsd_pair_xent_f32(_p(scores), 1.0 / tau, _p(r.get("row_loss")), _p(r.get("col_loss")), _p(r["row_argmax"]),
+                                        _p(r["col_argmax"]), _p(means), G, Pn, Q, _stream()), "avsd_pair_xent_f32")
+    if means is not None:
+        r.update(av_loss=means[0], va_loss=means[1], av_acc=means[2], va_acc=means[3])
+    return r
 
 
 def maxpool_hw_f32(x: torch.Tensor) -> torch.Tensor:

@@ -656,6 +656,34 @@ int avsd_resize_aa_normalize_f32(const float* x, float* tmp, float* out, int n_i
                                  const int* y_start, const int* y_count, const float* y_weight, int y_taps,
                                  const int* x_start, const int* x_count, const float* x_weight, int x_taps, int crop,
                                  float mean0, float mean1, float mean2, float std0, float std1, float std2, void* stream);
+/* The FC head on a MATRIX of pairs (csrc/avsync_pairs.hip): scripts/avsync_eval.py:138-148 scores one audio against k videos and k
+ * audios against one video, avsync/models/sync_contrastive_trainer.py:35-38 all k x k pairs of an example.  The head's first layer is
+ * linear in cat(a, v), so with U[g, p] = Wa . a[g, p] and Vh[g, q] = Wv . v[g, q] + b1 (two avsd_convnd_f32 calls on the column
+ * halves of the packed W1 [H1][2 D]: ldw = 2 D, cin = D, the weight pointer at column 0 and at column D, no ReLU)
+ *   scores[(g * P + p) * Q + q] = b3[0] + sum_n w3[n] * relu(b2[n] + sum_k W2[n * ldw2 + k] * relu(U[g, p, k] + Vh[g, q, k]))
+ * for g < G, p < P, q < Q, n < H2, k < H1.  U [G][P][H1], Vh [G][Q][H1], W2 [H2][ldw2 >= H1], b2 [H2], w3 = row 0 of the last
+ * layer's weight (the reference reads [:, 0]), b3 its bias (element 0 is read); b2 and b3 may be NULL (zero).  One launch: rows of
+ * the product are pairs, it runs on v_mfma_f32_32x32x2_f32 with relu(U + Vh) formed on the way into the fragments; neither the
+ * (G P Q, 2 D) concatenation nor the (G P Q, H1) hidden layer exists in memory.  The sum over k is the k-ordered chain 0 .. H1-1,
+ * the sum over n a fixed tree (by H2 alone): a pair's score depends on its U row, its Vh row and the weights only — not on G, P, Q
+ * or on where the pair sits.  H1 a multiple of 32, H2 a multiple of 32 up to 256 (the real head: 512 / 256), ldw2 a multiple of 4,
+ * U, Vh, W2 16-byte aligned; anything else is AVSD_EINVAL before a launch (asva_amd/avsync.py then takes the materialised path).
+ * Exactly G * P * Q floats are written. */
+int avsd_pair_head_f32(const float* U, const float* Vh, const float* W2, int ldw2, const float* b2, const float* w3, const float* b3,
+                       float* scores, int G, int P, int Q, int H1, int H2, void* stream);
+/* The contrastive objective on a score matrix scores [G][P][Q] (sync_contrastive_trainer.py:40-53), x = scores * inv_tau:
+ *   row_loss[g, p]   = -log softmax_q(x[g, p, :])[p]           written when P <= Q (the label of row p is q = p)
+ *   col_loss[g, q]   = -log softmax_p(x[g, :, q])[q]           written when Q <= P
+ *   row_argmax[g, p] = argmax_q scores[g, p, q], col_argmax[g, q] = argmax_p scores[g, p, q]      int32, always written;
+ *                      a tie goes to the lowest index
+ *   means[0 .. 3]    = av_loss = mean row_loss, va_loss = mean col_loss, av_acc = mean(row_argmax[g, p] == p), va_acc = mean(
+ *                      col_argmax[g, q] == q)                  written when P == Q
+ * The maximum is subtracted before exp, so scores of any finite size give a finite loss, and a 1 x 1 matrix gives exactly 0.
+ * Deterministic, no atomics, two launches (one when P != Q): a wave folds each line in f32 in a fixed tree; the means are folded
+ * in double in a fixed tree.  A line's loss and argmax therefore depend neither on G nor on g.  Pointers of outputs that are not
+ * written may be NULL; outputs may overlap neither scores nor each other. */
+int avsd_pair_xent_f32(const float* scores, float inv_tau, float* row_loss, float* col_loss, int32_t* row_argmax, int32_t* col_argmax,
+                       float* means, int G, int P, int Q, void* stream);
 
 /* ---- CLIP text encoder (asva_amd/text_encoder.py; csrc/clip_text.hip) --------------------------------------------------------
  * The text_encoder of Stable Diffusion 1.5 (CLIP ViT-L/14 text tower: token + position embedding, 12 pre-LN blocks with causal
